@@ -14,13 +14,20 @@
   ``hamer_light`` = configs[2] (bz=64), ``handoccnet_light`` = configs[3] (bz=256 GLOBAL, 256/N per GPU),
   ``mano_lbs`` = configs[4] (1024 crops GLOBAL, 1024/N per GPU, all-gather of the 778x3 vertices):
   strong scaling.
-* Inputs are resident in HBM before the timed region; outputs stay on the device.
+* Inputs are resident in HBM before the timed region; outputs stay on the device.  The inputs and weights are seeded: the
+  same arguments give the same inputs in every run.
 
-Output (rank 0): stdout carries exactly ONE line, the headline: a JSON object below 4 KB (``compact_headline``).  At N=1 the
-default run also writes one short JSON line per extra measurement to STDERR (``{"also": "<name>", ...}``: BASELINE configs
+A plain run (no ``--full``) sets up, warms up, times the K steps and prints the headline: ``value`` / ``ms_per_step`` and
+the config; ``roofline``, ``cpu_baseline`` and ``parity`` are null.  ``--dump-outputs DIR`` writes what the last timed
+step returned (``dump_outputs``) so that two builds can be compared output for output.  ``--full`` adds everything
+else described below (counter passes, measured ceilings, the one-stream roofline pass, CPU baseline, parity, the extra
+configurations); the ``--no-*`` switches trim that run.
+
+Output (rank 0): stdout carries exactly ONE line, the headline: a JSON object below 4 KB (``compact_headline``).  At N=1 a
+``--full`` run also writes one short JSON line per extra measurement to STDERR (``{"also": "<name>", ...}``: BASELINE configs
 3-5 and the separately reported arithmetic modes, each with roofline + cpu_baseline + parity; the headline carries their
-values as ``also: {name: hands/s}``); the per-kernel / per-launch-shape tables of everything go to
-``gpurun_out/bench_details.json``.  What the keys mean is DESIGN.md section 5:
+values as ``also: {name: hands/s}``); the per-kernel / per-launch-shape tables of everything go to ``bench_details.json``
+(the headline's ``details`` key names the file).  What the keys mean is DESIGN.md section 5:
 ``roofline`` covers the MFMA kernels (conv_igemm_f32 family + conv_wino_f32 + the fused stem): achieved = algorithmic
 FLOPs of all their launches in one step / the summed duration of those launches, each bracketed by HIP events on the
 launch stream in ``mode: "serial"`` (one HIP stream, every launch alone on the chip -- the mode the rocprofv3 per-kernel
@@ -75,7 +82,17 @@ def parse_args(argv=None):
                          "of this process: 30-90 s per workload, up to 2 x 150 s); roofline.traffic then comes from a stored summary "
                          "whose csrc_sha16 equals the loaded library's, or is null")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)   # the profiled child: two one-stream forwards
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also take every measurement beyond the timed steps: counter passes, measured ceilings, the one-stream "
+                         "roofline pass, host / D2H / all-gather timings, CPU baseline, parity, the extra configurations")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.layer_report and not args.full:
+        ap.error("--layer-report comes from the one-stream roofline pass: add --full")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -393,13 +410,15 @@ class Ctx:
         return [float(p.item()) for p in parts]
 
     def timed(self, step, steps, warmup):
-        """W untimed steps, then exactly K steps between barrier + synchronize pairs; max over ranks."""
+        """W untimed steps, then exactly K steps between barrier + synchronize pairs; max over ranks.  The last step's result
+        is kept in ``last_out`` (no earlier step's result outlives its step, as before)."""
         for _ in range(warmup):
             step()
         self.fence()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - 1):
             step()
+        self.last_out = step()
         self.fence()
         self.last_local_seconds = time.perf_counter() - t0      # this rank's own clock (per-rank rates)
         return self.max_over_ranks(self.last_local_seconds)
@@ -458,6 +477,39 @@ def measure_ceilings(ctx):
     torch.cuda.empty_cache()
     CEILINGS["source"] = "same-run: hands_ceiling_mfma_f32 (3000 x 32 MFMA per wave, 2 waves / SIMD) and hands_ceiling_hbm_read_f32 (2 GiB), best of 3"
     return CEILINGS
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out, path):
+    """--dump-outputs: every tensor of ``out`` (the last timed step's result, joined) as ``path/<key>.npy``: float64 stays
+    float64, integer and boolean outputs become float64 (exact), every other floating type float32.  Should the set exceed
+    64 MB, each array keeps the same fixed, seeded sample of its rows in every run.  Called before anything else runs on the
+    device: a later forward may overwrite the buffers the outputs live in."""
+    import numpy as np
+    import torch
+    arrays = {}
+    for k, v in dict(out.items()).items():
+        if not torch.is_tensor(v):
+            continue
+        v = v.detach()
+        if v.dtype != torch.float64:
+            v = v.to(torch.float32 if v.is_floating_point() else torch.float64)
+        arrays[k] = v.cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        frac = DUMP_LIMIT_BYTES / total
+        for k, a in arrays.items():
+            if a.ndim and a.shape[0] > 1:
+                idx = np.sort(np.random.default_rng(0).choice(a.shape[0], max(1, int(a.shape[0] * frac)), replace=False))
+                arrays[k] = a[idx]
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k.replace(os.sep, "_") + ".npy"), a)
+    nbytes = sum(a.nbytes for a in arrays.values())
+    sys.stderr.write(f"bench.py: wrote {len(arrays)} arrays ({nbytes / 1e6:.1f} MB) to {path}\n")
+    return len(arrays)
 
 
 def default_bz(workload, world):
@@ -542,9 +594,10 @@ def forward_with_d2h_ms(ctx, model, inputs, meta, n):
 
 
 def measure_model(ctx, workload, bz, steps, warmup, args, serial_headline=False, parity_bz=0, layer_report="", math="fp32",
-                  winograd=None, winograd_scope=None, graph=0):
+                  winograd=None, winograd_scope=None, graph=0, full=True, dump=""):
     """Returns (result dict, model, cpu state_dict) -- result holds value / ms_per_step / roofline / serial /
-    overlapped (+ parity vs the oracle on ``parity_bz`` samples when > 0, rank 0 only)."""
+    overlapped (+ parity vs the oracle on ``parity_bz`` samples when > 0, rank 0 only).  ``full=False``: value /
+    ms_per_step only, nothing runs after the timed steps.  ``dump``: directory for the last timed step's outputs."""
     torch = ctx.torch
     import hands_amd
     from hands_amd.dist import gather_predictions
@@ -604,6 +657,15 @@ def measure_model(ctx, workload, bz, steps, warmup, args, serial_headline=False,
         return g
 
     elapsed = ctx.timed(step, steps, warmup)
+    if dump and ctx.rank == 0:
+        dump_outputs(ctx.last_out, dump)
+    ctx.last_out = None
+    if not full:
+        if ctx.rank != 0:
+            return None, model, None
+        hands_per_s = ctx.world * 2 * bz * steps / elapsed
+        return ({"value": round(hands_per_s, 1), "ms_per_step": round(elapsed / steps * 1e3, 3),
+                 "hands_per_sec_per_gpu": round(hands_per_s / ctx.world, 1)}, model, sd_cpu)
     enqueue_ms = host_enqueue_ms(ctx, step)
     rank_rates = ctx.gather_floats(2 * bz * steps / ctx.last_local_seconds)
     # (both through `fwd`, the execution mode `value` was measured in: the hipGraph replay when --graph is set)
@@ -1020,9 +1082,10 @@ def cpu_baseline_small(ctx, wl, model, sd_cpu, cb):
 # ------------------------------------------------------------------------------------------------------
 # config 5: two-hand MANO LBS alone
 # ------------------------------------------------------------------------------------------------------
-def measure_lbs(ctx, bz, steps, warmup, with_cpu=True):
+def measure_lbs(ctx, bz, steps, warmup, with_cpu=True, full=True, dump=""):
     """configs[4]: a step = ONE pre-bound C-ABI call (hands_amd.ManoHeadsPlan.launch -> hands_mano_heads_f32: both hands'
-    MANOHead.forward, mano_head.py:21-65) over fixed device buffers, + the all-gather of the vertices when N > 1."""
+    MANOHead.forward, mano_head.py:21-65) over fixed device buffers, + the all-gather of the vertices when N > 1.
+    ``full`` / ``dump`` as in measure_model."""
     torch = ctx.torch
     import hands_amd
     from hands_amd import _lib
@@ -1061,6 +1124,15 @@ def measure_lbs(ctx, bz, steps, warmup, with_cpu=True):
 
     out = step()
     elapsed = ctx.timed(step, steps, warmup)
+    if dump and ctx.rank == 0:
+        dump_outputs(ctx.last_out, dump)
+    ctx.last_out = None
+    if not full:
+        if ctx.rank != 0:
+            return None
+        hands = ctx.world * 2 * bz * steps / elapsed
+        return {"value": round(hands, 1), "ms_per_step": round(elapsed / steps * 1e3, 4),
+                "hands_per_sec_per_gpu": round(hands / ctx.world, 1)}
     enqueue_ms = host_enqueue_ms(ctx, step)
     rank_rates = ctx.gather_floats(2 * bz * steps / ctx.last_local_seconds)
     gather_us = allgather_us(ctx, lambda: verts) if ctx.world > 1 and not ctx.host_collective else None
@@ -1238,7 +1310,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.graph < 0:                         # auto: the fastest bit-identical mode of config 4's shard size
         args.graph = 4 if (args.workload == "handoccnet_light" and world > 1 and not args.serial and not args.latency_mode) else 0
-    if (world == 1 and args.workload != "mano_lbs" and not args.no_pmc and not args.latency_mode and not args.graph
+    if (args.full and world == 1 and args.workload != "mano_lbs" and not args.no_pmc and not args.latency_mode and not args.graph
             and not os.environ.get("HANDS_BENCH_PMC_CHILD") and not os.environ.get("ROCPROFILER_LIBRARY_CTOR")
             and "rocprof" not in os.environ.get("LD_PRELOAD", "") and not os.environ.get("HANDS_BENCH_SHIPPED_ONLY")):
         # before the first GPU call of this process: the counter passes are children with their own GPU context
@@ -1270,15 +1342,17 @@ def main():
     first = rank0 = ctx.rank == 0
     full, also = None, {}
     if wl == "mano_lbs":
-        res = measure_lbs(ctx, bz, args.steps, args.warmup, with_cpu=not args.no_cpu_baseline)
+        res = measure_lbs(ctx, bz, args.steps, args.warmup, with_cpu=not args.no_cpu_baseline, full=args.full,
+                          dump=args.dump_outputs)
         model = None
     else:
-        want_parity = first and not args.no_cpu_baseline and ctx.world == 1
+        want_parity = args.full and first and not args.no_cpu_baseline and ctx.world == 1
         res, model, sd_cpu = measure_model(ctx, wl, bz, args.steps, args.warmup, args, serial_headline=args.serial,
-                                           parity_bz=8 if want_parity else 0, layer_report=args.layer_report, graph=args.graph)
+                                           parity_bz=8 if want_parity else 0, layer_report=args.layer_report, graph=args.graph,
+                                           full=args.full, dump=args.dump_outputs)
     if rank0:
         cpu_baseline, parity = res.pop("cpu_baseline", None), res.pop("parity", None)
-        if wl != "mano_lbs" and not args.no_cpu_baseline and ctx.world == 1:
+        if args.full and wl != "mano_lbs" and not args.no_cpu_baseline and ctx.world == 1:
             if wl == "hands_light":
                 cpu_baseline, parity = cpu_baseline_hands_light(ctx, model, sd_cpu)
             else:
@@ -1302,7 +1376,7 @@ def main():
             "cpu_baseline": cpu_baseline, "parity": parity})
 
     # ---- BASELINE configs 3-5 in the same run (N=1, headline workload only): one short line each ------
-    if rank0 and wl == "hands_light" and ctx.world == 1 and not args.no_also:
+    if args.full and rank0 and wl == "hands_light" and ctx.world == 1 and not args.no_also:
         del model
         torch.cuda.empty_cache()
         t_also = time.perf_counter()
@@ -1356,7 +1430,7 @@ def main():
             emit_also("mano_lbs", {"error": f"{type(e).__name__}: {e}"[:300]})
         full["also_seconds"] = round(time.perf_counter() - t_also, 1)
     if rank0:
-        details = write_details(full, also)
+        details = write_details(full, also) if args.full else None
         print(json.dumps(compact_headline(full, also, details)), flush=True)       # the headline: the only stdout line, < 4 KB
     ctx.close()
 

@@ -147,3 +147,37 @@ def test_also_lines_stay_below_their_limit(bench):
         line = bench.compact_also(v, k)
         assert len(json.dumps(line)) < bench.ALSO_LIMIT == 2048, (k, len(json.dumps(line)))
         assert line["also"] == k and line["value"] == v["value"] and "frac" in line["roofline"]
+
+
+def test_plain_run_is_lean_by_default(bench):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` times the steps and nothing else; --full brings the rest back."""
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs == ""
+    assert bench.parse_args(["--full"]).full
+    for bad in (["--steps", "0"], ["--layer-report", "x.csv"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_the_same_rows(bench, tmp_path, monkeypatch, capsys):
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(0)
+    out = {"mano.vertices.r": torch.randn(64, 778, 3, generator=g), "cam.t": torch.randn(64, 3, dtype=torch.float64, generator=g),
+           "is_valid": torch.arange(64), "half": torch.randn(64, 2, generator=g).half(), "note": "not an array"}
+    assert bench.dump_outputs(out, str(tmp_path / "a")) == 4
+    v = np.load(tmp_path / "a" / "mano.vertices.r.npy")
+    assert v.dtype == np.float32 and np.array_equal(v, out["mano.vertices.r"].numpy())
+    assert np.load(tmp_path / "a" / "cam.t.npy").dtype == np.float64
+    assert np.array_equal(np.load(tmp_path / "a" / "is_valid.npy"), np.arange(64, dtype=np.float64))
+    assert np.load(tmp_path / "a" / "half.npy").dtype == np.float32
+    # above the limit: a fixed sample of rows, the same in every run
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 64 << 10)
+    bench.dump_outputs(out, str(tmp_path / "b"))
+    bench.dump_outputs(out, str(tmp_path / "c"))
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in files) < (64 << 10) + 4096
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))
+    vb = np.load(tmp_path / "b" / "mano.vertices.r.npy")
+    assert 0 < vb.shape[0] < 64 and any(np.array_equal(vb[0], r) for r in v)

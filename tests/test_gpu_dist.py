@@ -57,7 +57,7 @@ def test_bench_launcher_starts_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(HANDS_BENCH_SHARE_GPU="1", HANDS_BENCH_BACKEND="gloo", HANDS_BENCH_GLOO_DEVICE="1")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--bz", "8", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--bz", "8", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -73,12 +73,12 @@ def test_bench_launcher_starts_its_own_ranks():
 
 
 def test_bench_at_the_drivers_arguments_two_ranks():
-    """The exact command line the driver's SCALE run uses -- `python bench.py --gpus 2 --steps 20 --warmup 5`, default
-    workload and batch size (bz = 256 per rank) -- end to end once, on the 1-GPU box (both ranks on cuda:0, gloo staging
-    the device tensors): one parseable headline as the last stdout line."""
+    """The driver's SCALE command line -- `python bench.py --gpus 2 --steps 20 --warmup 5`, default workload and batch size
+    (bz = 256 per rank) -- with --full (the roofline and all-gather keys checked below), end to end once, on the 1-GPU box
+    (both ranks on cuda:0, gloo staging the device tensors): one parseable headline as the last stdout line."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(HANDS_BENCH_SHARE_GPU="1", HANDS_BENCH_BACKEND="gloo", HANDS_BENCH_GLOO_DEVICE="1")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--full"],
                        env=env, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-2000:]
     last = p.stdout.splitlines()[-1]
@@ -91,10 +91,10 @@ def test_bench_at_the_drivers_arguments_two_ranks():
 
 
 def test_bench_default_run_prints_one_stdout_line():
-    """`python bench.py` (N = 1, with the extra measurements of configs 3-5): stdout is exactly ONE line -- the headline with
+    """`python bench.py --full` (N = 1, with the extra measurements of configs 3-5): stdout is exactly ONE line -- the headline with
     roofline, cpu_baseline and parity -- below 4 KB; the extra measurements are short JSON lines on stderr."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--bz", "16"], env=env,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--bz", "16", "--full"], env=env,
                        capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-2000:]
     out = p.stdout.strip().splitlines()
@@ -108,6 +108,39 @@ def test_bench_default_run_prints_one_stdout_line():
     assert all(len(json.dumps(a)) < 2048 for a in also)
 
 
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path, recipe_model):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` (no --full): one headline line with the contract keys and nothing
+    measured beyond the K steps; --dump-outputs writes the 22 outputs of the last timed step, identical in two runs (seeded
+    inputs) and equal to the forward of the same inputs in this process."""
+    import copy
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    dumps = []
+    for run in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--bz", "4", "--dump-outputs", str(tmp_path / run)], env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        out = p.stdout.strip().splitlines()
+        assert len(out) == 1 and len(out[0]) < 4096
+        d = json.loads(out[0])
+        assert d["metric"] == "hands/sec" and d["unit"] == "hands/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["config"]["per_gpu_batch"] == 4
+        assert d["value"] > 0 and abs(d["value"] - 2 * 4 / (d["ms_per_step"] * 1e-3)) < 0.01 * d["value"]
+        assert d["roofline"] is None and d["cpu_baseline"] is None and d["parity"] is None and "also" not in d
+        dumps.append({f[:-4]: np.load(tmp_path / run / f) for f in os.listdir(tmp_path / run)})
+    assert len(dumps[0]) == 22 and dumps[0].keys() == dumps[1].keys()
+    for k, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, dumps[1][k]), k
+    model = copy.deepcopy(recipe_model).to("cuda")
+    model.overlap_trunks = True                  # bench.py's timed mode
+    inputs, meta = synthetic_inputs(4, 0, device="cuda")
+    ref = {k: v.detach().cpu().double().numpy() for k, v in model(inputs, meta).items()}
+    torch.cuda.synchronize()
+    assert ref.keys() == dumps[0].keys()
+    for k, a in dumps[0].items():
+        assert a.shape == ref[k].shape and np.allclose(a, ref[k], rtol=1e-5, atol=1e-6), k
+
+
 def test_bench_under_torchrun_two_ranks():
     """The driver's N > 1 command: `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
     --master-port P bench.py --gpus N ...` -- every process is a rank (no launcher), rank 0 prints the one headline.  Dry run on the
@@ -116,7 +149,7 @@ def test_bench_under_torchrun_two_ranks():
     env.update(HANDS_BENCH_SHARE_GPU="1", HANDS_BENCH_BACKEND="gloo", HANDS_BENCH_GLOO_DEVICE="1")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                         "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps",
-                        "3", "--warmup", "1", "--bz", "8", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "3", "--warmup", "1", "--bz", "8", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1 and p.stdout.strip().splitlines()[-1] == lines[0]
@@ -130,7 +163,7 @@ def test_bench_hamer_light_two_rank_dry_run():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(HANDS_BENCH_SHARE_GPU="1", HANDS_BENCH_BACKEND="gloo", HANDS_BENCH_GLOO_DEVICE="1")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--workload", "hamer_light", "--bz", "4", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
+                        "--workload", "hamer_light", "--bz", "4", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True,
                        timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads(p.stdout.splitlines()[-1])
@@ -146,7 +179,7 @@ def test_bench_strong_scaling_dry_runs(workload, global_bz):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(HANDS_BENCH_SHARE_GPU="1", HANDS_BENCH_BACKEND="gloo", HANDS_BENCH_GLOO_DEVICE="1")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--workload", workload, "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--workload", workload, "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1

@@ -3,7 +3,7 @@ export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; WL=$1; BZ=$2; shift 2
 for v in "$@"; do
   if [ "$v" = "-" ]; then unset HANDS_HIP_LIB; else export HANDS_HIP_LIB=$R/build_ab/$v.so; fi
   O=/tmp/fetch_$v; rm -rf $O; mkdir -p $O; cd /tmp
-  rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O -o f -- python3 $R/bench.py --workload $WL --bz $BZ --no-cpu-baseline --no-also --serial --steps 1 --warmup 1 > /dev/null 2> $O/err
+  rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O -o f -- python3 $R/bench.py --workload $WL --bz $BZ --full --no-cpu-baseline --no-also --serial --steps 1 --warmup 1 > /dev/null 2> $O/err
   F=$(find $O -name "*counter_collection.csv" | head -1)
   python3 - "$F" "$v" <<'PY'
 import csv,sys

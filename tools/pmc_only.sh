@@ -2,7 +2,7 @@
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; TAG=$1; WL=$2; O=$R/gpurun_out/$TAG/$WL
 mkdir -p $O; cd /tmp
-COMMON="--workload $WL --bz ${3:-256} --no-cpu-baseline --no-also --serial --steps 1 --warmup 1"
+COMMON="--workload $WL --bz ${3:-256} --full --no-cpu-baseline --no-also --serial --steps 1 --warmup 1"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -o fetch -- python3 $R/bench.py $COMMON > /dev/null 2> $O/fetch.err
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -o write -- python3 $R/bench.py $COMMON > /dev/null 2> $O/write.err
 cd $R

@@ -3,7 +3,7 @@
 # one-stream mode (stream-K launches where the library picks them)
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/pos; mkdir -p $O; cd /tmp
-C="--workload hands_light --bz 256 --no-cpu-baseline --no-also"
+C="--workload hands_light --bz 256 --full --no-cpu-baseline --no-also"
 python3 $R/bench.py $C --layer-report $O/per_launch.csv > $O/line.json 2>/dev/null
 if [ "$PMC_MODE" != "--serial" ]; then export HANDS_BENCH_SHIPPED_ONLY=1; fi
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -o fetch -- python3 $R/bench.py $C $PMC_MODE --steps 1 --warmup 1 > /dev/null 2> $O/fetch.err

@@ -1,7 +1,7 @@
 # usage (on the GPU box): bash tools/pmc_ta.sh <tag> <workload> [bz]   -- texture-unit busy fraction per kernel family
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$1; mkdir -p $O; cd /tmp
-timeout 300 rocprofv3 --pmc TA_TA_BUSY_sum GRBM_GUI_ACTIVE --output-format csv -d $O/ta -o p -- python3 $R/bench.py --workload $2 --bz ${3:-256} --no-cpu-baseline --no-also --no-sweep --serial --steps 1 --warmup 1 > /dev/null 2> $O/ta.err
+timeout 300 rocprofv3 --pmc TA_TA_BUSY_sum GRBM_GUI_ACTIVE --output-format csv -d $O/ta -o p -- python3 $R/bench.py --workload $2 --bz ${3:-256} --full --no-cpu-baseline --no-also --no-sweep --serial --steps 1 --warmup 1 > /dev/null 2> $O/ta.err
 echo "rc $?"
 cd $R
 python3 - $O <<'PY'
