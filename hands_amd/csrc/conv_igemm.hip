@@ -1075,6 +1075,8 @@ bool pointwise_route_ok(const hands_conv_desc* d) {
          (long long)(d->Ho - 1) * d->stride < d->H && (long long)(d->Wo - 1) * d->stride < d->W;
 }
 
+// Every entry's ConvArgs: one launch of the layer over its whole K from one source (the dual entry then sets its second source,
+// split-K its slices)
 void fill_plain_args(const hands_conv_desc* d, const float* in, const float* w_packed, const float* bias, const float* residual,
                      float* out, const float* pre_scale, const float* pre_shift, ConvArgs& a) {
   a.in = in; a.w = w_packed; a.bias = bias; a.res = residual; a.out = out;
@@ -1086,6 +1088,24 @@ void fill_plain_args(const hands_conv_desc* d, const float* in, const float* w_p
   a.ksplit = 1; a.partial = nullptr; a.part_ps = 0; a.pre_scale = pre_scale; a.pre_shift = pre_shift;
   a.in2 = in; a.K0 = 1 << 30; a.H2 = a.W2 = a.stride2 = a.in2_ps = 0;
   a.nblk_m = a.nblk_n = 0;
+}
+
+// The conv_igemm_f32_kernel instantiation a launch runs -- the one place that picks it.  The stem (Cin == 4) has one form, MODE 1;
+// a `pre` layer the exact-fp32 / fp64 forms of the pointwise MODE 2 (its entry rejects bf16x3); `bf16x3`, where the entry honours
+// it, PREC 1; otherwise exact fp32 or fp64 with the summation block the descriptor asks for (launch_fp32).  Pointwise layers and
+// the dual entry's two sources (K0 < Kpad: the k-loop switches source at K0) take MODE 2, every other convolution MODE 0.
+int launch_conv(const hands_conv_desc* d, ConvArgs& a, bool pre, bool bf16x3, hipStream_t s) {
+  const bool narrow = d->Cout <= 64;
+  if (d->Cin == 4) return narrow ? launch<4, 1, 1>(a, s) : launch<2, 2, 1>(a, s);
+  if (pre) return launch_fp32<2, true>(d, a, s);
+  // pointwise layers (1x1, no padding; any stride) take the two-source instantiation with the switch
+  // point out of reach: no tap state and no bounds checks in the k-loop
+  const bool pointwise = a.K0 < a.Kpad || pointwise_route_ok(d);
+  if (bf16x3) {
+    if (pointwise) return narrow ? launch<4, 1, 2, 1>(a, s) : launch<2, 2, 2, 1>(a, s);
+    return narrow ? launch<4, 1, 0, 1>(a, s) : launch<2, 2, 0, 1>(a, s);
+  }
+  return pointwise ? launch_fp32<2>(d, a, s) : launch_fp32<0>(d, a, s);
 }
 
 // The kernel instantiation a POINTWISE layer runs (the unit a grouped launch is homogeneous in), or -1 when the layer cannot
@@ -1119,7 +1139,7 @@ extern "C" int hands_conv2d_group_class(const hands_conv_desc* d, int pre) { ret
 
 extern "C" int hands_conv2d_group_f32(const hands_conv_job* jobs, int n, hands_stream_t stream) {
   if (!jobs || n < 1 || n > GROUP_MAX) return HANDS_EINVAL;
-  GroupArgs g;
+  GroupArgs g{};
   g.n = n;
   int cls = -2;
   for (int p = 0; p < n; ++p) {
@@ -1159,26 +1179,9 @@ extern "C" int hands_conv2d_nhwc_f32(const hands_conv_desc* d, const float* in, 
                                      hands_stream_t stream) {
   if (!d || !in || !w_packed || !bias || !out) return HANDS_EINVAL;
   if (!conv_geometry_ok(d)) return HANDS_EINVAL;
-  const bool stem = d->Cin == 4;
   ConvArgs a;
-  a.in = in; a.w = w_packed; a.bias = bias; a.res = residual; a.out = out;
-  a.M = d->B * d->Ho * d->Wo; a.N = d->Cout; a.Kpad = d->Kpad;
-  a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo;
-  a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
-  a.in_ps = d->in_pix_stride; a.out_ps = d->out_pix_stride; a.res_ps = d->res_pix_stride;
-  a.relu = d->act & HANDS_ACT_MASK;
-  a.ksplit = 1; a.partial = nullptr; a.part_ps = 0; a.pre_scale = nullptr; a.pre_shift = nullptr;
-  a.in2 = in; a.K0 = 1 << 30; a.H2 = a.W2 = a.stride2 = a.in2_ps = 0;
-  hipStream_t s = (hipStream_t)stream;
-  if (stem) return (d->Cout <= 64) ? launch<4, 1, 1>(a, s) : launch<2, 2, 1>(a, s);
-  if (d->act & HANDS_MATH_BF16X3) {
-    if (pointwise_route_ok(d)) return (d->Cout <= 64) ? launch<4, 1, 2, 1>(a, s) : launch<2, 2, 2, 1>(a, s);
-    return (d->Cout <= 64) ? launch<4, 1, 0, 1>(a, s) : launch<2, 2, 0, 1>(a, s);
-  }
-  // pointwise layers (1x1, no padding; any stride) take the two-source instantiation with the switch
-  // point out of reach: no tap state and no bounds checks in the k-loop
-  if (pointwise_route_ok(d)) return launch_fp32<2>(d, a, s);
-  return launch_fp32<0>(d, a, s);
+  fill_plain_args(d, in, w_packed, bias, residual, out, nullptr, nullptr, a);
+  return launch_conv(d, a, false, (d->act & HANDS_MATH_BF16X3) != 0, (hipStream_t)stream);
 }
 
 extern "C" long long hands_conv2d_streamk_workspace_bytes(void) {
@@ -1198,18 +1201,11 @@ extern "C" int hands_conv2d_nhwc_streamk_f32(const hands_conv_desc* d, const flo
                                              long long workspace_bytes, int epoch, hands_stream_t stream) {
   if (!d || !in || !w_packed || !bias || !out) return HANDS_EINVAL;
   if (!conv_geometry_ok(d)) return HANDS_EINVAL;
-  if (d->Cin == 4) return hands_conv2d_nhwc_f32(d, in, w_packed, bias, residual, out, stream);   // the stem has its own kernel
-  ConvArgs a;
-  a.in = in; a.w = w_packed; a.bias = bias; a.res = residual; a.out = out;
-  a.M = d->B * d->Ho * d->Wo; a.N = d->Cout; a.Kpad = d->Kpad;
-  a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo;
-  a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
-  a.in_ps = d->in_pix_stride; a.out_ps = d->out_pix_stride; a.res_ps = d->res_pix_stride;
-  if (d->act & (HANDS_MATH_BF16X3 | HANDS_SUM_BLOCK128 | HANDS_SUM_BLOCK64 | HANDS_ACC_F64))
+  // the stem has its own kernel; a flagged descriptor is not one fp32 chain: both take the plain entry
+  if (d->Cin == 4 || (d->act & (HANDS_MATH_BF16X3 | HANDS_SUM_BLOCK128 | HANDS_SUM_BLOCK64 | HANDS_ACC_F64)))
     return hands_conv2d_nhwc_f32(d, in, w_packed, bias, residual, out, stream);
-  a.relu = d->act & HANDS_ACT_MASK;
-  a.ksplit = 1; a.partial = nullptr; a.part_ps = 0; a.pre_scale = nullptr; a.pre_shift = nullptr;
-  a.in2 = in; a.K0 = 1 << 30; a.H2 = a.W2 = a.stride2 = a.in2_ps = 0;
+  ConvArgs a;
+  fill_plain_args(d, in, w_packed, bias, residual, out, nullptr, nullptr, a);
   hipStream_t s = (hipStream_t)stream;
   if (pointwise_route_ok(d))
     return (d->Cout <= 64) ? launch_streamk<4, 1, 2>(a, s, workspace, workspace_bytes, epoch)
@@ -1236,24 +1232,19 @@ extern "C" int hands_conv1x1_dual_nhwc_f32(const hands_conv_desc* d, const float
         256LL * d->Kpad * 4 >= (1LL << 31))
       return HANDS_EINVAL;
   }
+  if (d->act & HANDS_ACC_F64) return HANDS_EINVAL;           // the two-source launch has no fp64 form
   ConvArgs a;
-  a.in = in; a.w = w_packed; a.bias = bias; a.res = nullptr; a.out = out;
-  a.M = d->B * d->Ho * d->Wo; a.N = d->Cout; a.Kpad = d->Kpad;
-  a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo;
-  a.KH = 1; a.KW = 1; a.stride = 1; a.pad = 0;
-  a.in_ps = d->in_pix_stride; a.out_ps = d->out_pix_stride; a.res_ps = 0;
-  a.relu = d->act & HANDS_ACT_MASK;
-  a.ksplit = 1; a.partial = nullptr; a.part_ps = 0; a.pre_scale = nullptr; a.pre_shift = nullptr;
+  fill_plain_args(d, in, w_packed, bias, nullptr, out, nullptr, nullptr, a);
   a.in2 = in2; a.K0 = d->Cin; a.H2 = H2; a.W2 = W2; a.stride2 = stride2; a.in2_ps = in2_pix_stride;
-  hipStream_t s = (hipStream_t)stream;
-  if (d->act & HANDS_MATH_BF16X3) return (d->Cout <= 64) ? launch<4, 1, 2, 1>(a, s) : launch<2, 2, 2, 1>(a, s);
-  return (d->Cout <= 64) ? launch<4, 1, 2>(a, s) : launch<2, 2, 2>(a, s);
+  hands_conv_desc one_chain = *d;                             // the block flags do not apply here
+  one_chain.act &= ~(HANDS_SUM_BLOCK128 | HANDS_SUM_BLOCK64);
+  return launch_conv(&one_chain, a, false, (d->act & HANDS_MATH_BF16X3) != 0, (hipStream_t)stream);
 }
 
 namespace {
-int pre_launch(const hands_conv_desc* d, const float* in, const float* pre_scale, const float* pre_shift,
-               const float* w_packed, const float* bias, const float* residual, float* out, hands_stream_t stream);
-
+// The split-K entries and the pre entry: the layer in S K-slices (raw partial sums to the workspace, then the reduction), or in one
+// launch when S <= 1 or the workspace is too small -- for a plain layer that is the hands_conv2d_nhwc_f32 call.  A split launch
+// runs a bf16x3 descriptor as exact fp32; its reduction is fused into the launch when `counters` cover its tiles.
 int splitk_launch(const hands_conv_desc* d, const float* in, const float* w_packed, const float* bias, const float* residual,
                   float* out, int S, float* workspace, long long workspace_floats,
                   hands_stream_t stream, const float* pre_scale = nullptr, const float* pre_shift = nullptr,
@@ -1265,35 +1256,22 @@ int splitk_launch(const hands_conv_desc* d, const float* in, const float* w_pack
   const int part_ps = d->Cout;                          // Cout % 4 == 0
   if (S > d->Kpad / BK) S = d->Kpad / BK;
   const bool f64 = (d->act & HANDS_ACC_F64) != 0;       // fp64 accumulation: the partial sums are doubles (twice the workspace)
-  if (S <= 1 || !workspace || workspace_floats < (long long)S * M * part_ps * (f64 ? 2 : 1) || (f64 && (((uintptr_t)workspace) & 7)))
-    return pre ? pre_launch(d, in, pre_scale, pre_shift, w_packed, bias, residual, out, stream)
-               : hands_conv2d_nhwc_f32(d, in, w_packed, bias, residual, out, stream);
-  if (!in || !w_packed || !bias || !out || !conv_geometry_ok(d) || S > 64) return HANDS_EINVAL;
-  const bool stem = d->Cin == 4;
+  const bool split = S > 1 && workspace && workspace_floats >= (long long)S * M * part_ps * (f64 ? 2 : 1) &&
+                     !(f64 && (((uintptr_t)workspace) & 7));
+  if (!split && !pre) return hands_conv2d_nhwc_f32(d, in, w_packed, bias, residual, out, stream);
+  if (!in || !w_packed || !bias || !out || !conv_geometry_ok(d) || (split && S > 64)) return HANDS_EINVAL;
   ConvArgs a;
-  a.pre_scale = pre_scale; a.pre_shift = pre_shift;
-  a.in = in; a.w = w_packed; a.bias = bias; a.res = nullptr; a.out = out;
-  a.M = (int)M; a.N = d->Cout; a.Kpad = d->Kpad;
-  a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo;
-  a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
-  a.in_ps = d->in_pix_stride; a.out_ps = d->out_pix_stride; a.res_ps = d->res_pix_stride;
-  a.relu = HANDS_ACT_NONE;
-  a.ksplit = S; a.partial = workspace; a.part_ps = part_ps;
-  a.in2 = in; a.K0 = 1 << 30; a.H2 = a.W2 = a.stride2 = a.in2_ps = 0;
-  {
+  fill_plain_args(d, in, w_packed, bias, residual, out, pre_scale, pre_shift, a);
+  if (split) {
+    a.ksplit = S; a.partial = workspace; a.part_ps = part_ps;     // (the slices ignore a.res / a.relu)
     // fused reduction when the caller's counter array covers the tiles of the instantiation this launch takes
     const bool narrow = d->Cout <= 64 && !f64;
     const long long ntiles = narrow ? ((M + 255) / 256) * ((d->Cout + 63) / 64) : ((M + 127) / 128) * ((d->Cout + 127) / 128);
     if (counters && n_counters >= ntiles) { a.counters = counters; a.fin_res = residual; a.fin_act = d->act & HANDS_ACT_MASK; }
   }
   hipStream_t s = (hipStream_t)stream;
-  int rc;
-  if (pre) rc = launch_fp32<2, true>(d, a, s);
-  else if (stem) rc = (d->Cout <= 64) ? launch<4, 1, 1>(a, s) : launch<2, 2, 1>(a, s);
-  else if (pointwise_route_ok(d)) rc = launch_fp32<2>(d, a, s);
-  else rc = launch_fp32<0>(d, a, s);
-  if (rc) return rc;
-  if (a.counters != nullptr) return 0;                  // the last slice of every tile has reduced it
+  const int rc = launch_conv(d, a, pre, false, s);
+  if (rc || !split || a.counters != nullptr) return rc;   // (fused: the last slice of every tile has reduced it)
   if (f64) {
     hipLaunchKernelGGL(splitk_reduce_f64_kernel, dim3(hands_grid_1d(M * d->Cout, 256)), dim3(256), 0, s,
                        reinterpret_cast<const double*>(workspace), S, (int)M, d->Cout, part_ps, bias, residual, d->res_pix_stride,
@@ -1305,32 +1283,14 @@ int splitk_launch(const hands_conv_desc* d, const float* in, const float* w_pack
                      d->Cout / 4, part_ps, bias, residual, d->res_pix_stride, out, d->out_pix_stride, d->act & HANDS_ACT_MASK);
   return (int)hipGetLastError();
 }
-int pre_launch(const hands_conv_desc* d, const float* in, const float* pre_scale, const float* pre_shift,
-               const float* w_packed, const float* bias, const float* residual, float* out, hands_stream_t stream) {
-  if (!d || !in || !pre_scale || !pre_shift || !w_packed || !bias || !out) return HANDS_EINVAL;
-  if (!conv_geometry_ok(d) || !pointwise_route_ok(d) || (d->act & HANDS_MATH_BF16X3)) return HANDS_EINVAL;
-  ConvArgs a;
-  a.in = in; a.w = w_packed; a.bias = bias; a.res = residual; a.out = out;
-  a.M = d->B * d->Ho * d->Wo; a.N = d->Cout; a.Kpad = d->Kpad;
-  a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo;
-  a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
-  a.in_ps = d->in_pix_stride; a.out_ps = d->out_pix_stride; a.res_ps = d->res_pix_stride;
-  a.relu = d->act & HANDS_ACT_MASK;
-  a.ksplit = 1; a.partial = nullptr; a.part_ps = 0;
-  a.pre_scale = pre_scale; a.pre_shift = pre_shift;
-  a.in2 = in; a.K0 = 1 << 30; a.H2 = a.W2 = a.stride2 = a.in2_ps = 0;
-  hipStream_t s = (hipStream_t)stream;
-  return launch_fp32<2, true>(d, a, s);
-}
 }  // namespace
 
 extern "C" int hands_conv2d_nhwc_pre_f32(const hands_conv_desc* d, const float* in, const float* pre_scale,
                                          const float* pre_shift, const float* w_packed, const float* bias,
                                          const float* residual, float* out, int S, float* workspace,
                                          long long workspace_floats, hands_stream_t stream) {
-  if (S > 1) return splitk_launch(d, in, w_packed, bias, residual, out, S, workspace, workspace_floats, stream,
-                                  pre_scale, pre_shift);
-  return pre_launch(d, in, pre_scale, pre_shift, w_packed, bias, residual, out, stream);
+  if (!pre_scale || !pre_shift) return HANDS_EINVAL;
+  return splitk_launch(d, in, w_packed, bias, residual, out, S, workspace, workspace_floats, stream, pre_scale, pre_shift);
 }
 
 extern "C" int hands_conv2d_nhwc_splitk_n_f32(const hands_conv_desc* d, const float* in, const float* w_packed,

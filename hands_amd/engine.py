@@ -10,6 +10,7 @@ the wrapper's ground-truth MANO pass).
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple
 
 import torch
 
@@ -119,9 +120,8 @@ class ConvEngine:
             raise RuntimeError(f"hands_amd: hipStreamIsCapturing failed: {L.hands_error_string(-st).decode()}")
         return bool(st)
 
-    def _workspace(self, L, dev, stream, need):
+    def _workspace(self, dev, stream, need, capturing):
         key = (dev, stream)
-        capturing = self._capturing(L, stream)
         # a launch recorded into a hipGraph gets a workspace from the graph's own memory pool (torch allocates from it
         # during capture) and never shares one with eager launches: the capture stream's handle can be recycled
         table = self._capture_ws if capturing else self._splitk_ws
@@ -149,103 +149,104 @@ class ConvEngine:
             torch.cuda.current_stream(dev).synchronize()     # zero fill done before a side stream uses it
         return c
 
-    def conv(self, L, pc, x, B, H, W, out, relu, stream, res=None, in_ps=None, out_ps=None, res_ps=None,
-             x_off=0, out_off=0, res_off=0, splitk=False, splitk_n=0, pre=None):
-        """One convolution / linear layer.  ``splitk=True`` marks rows that are per-SAMPLE (head MLPs): only
-        there may the library cut K by its own (layer-only) policy -- token / pixel GEMMs would cross the
-        library's row threshold between batch sizes and lose bit-reproducibility.  ``splitk_n`` is a
-        call-site constant slice count (summation order independent of the batch size)."""
+    def _desc(self, pc, B, H, W, act, in_ps, out_ps, res_ps, has_res):
+        """The descriptor of one layer launch; act: bool or a HANDS_ACT_* code (the route adds its flags)."""
         Ho = (H + 2 * pc.pad - pc.KH) // pc.stride + 1
         Wo = (W + 2 * pc.pad - pc.KW) // pc.stride + 1
-        d = ConvDesc(B, H, W, pc.Cin, Ho, Wo, pc.Cout, pc.KH, pc.KW, pc.stride, pc.pad,
-                     in_ps or pc.Cin, out_ps or pc.Cout,
-                     (pc.Cout if res_ps is None else res_ps) if res is not None else 0,
-                     pc.Kpad, int(relu) | (MATH_BF16X3 if self.math == "bf16x3" else 0))   # relu: bool or a HANDS_ACT_* code
-        hook = self.hook
-        self.last_sum_block = 0
-        acc64 = self.last_acc64 = bool(self.acc64 and pc.acc64 and self.math == "fp32" and pc.Cin != 4)
-        S = L.hands_conv2d_splitk_factor(C.byref(d)) if (splitk and self.use_splitk) else 1
-        if splitk_n > 1 and self.use_splitk:
-            S = splitk_n
-        if self.latency_mode:
-            # small-batch serving: a layer with a handful of output tiles walks a K of 2304-4608 serially
-            # on a few CUs; cut K so that ~256 workgroups exist, at least 8 k-steps (128 floats) per slice
-            bm, bn = (256, 64) if pc.Cout <= 64 else (128, 128)
-            tiles = -(-(B * Ho * Wo) // bm) * -(-pc.Cout // bn)
-            S = max(S, min(256 // tiles, pc.Kpad // 128, 32)) if tiles <= 128 else S
+        return ConvDesc(B, H, W, pc.Cin, Ho, Wo, pc.Cout, pc.KH, pc.KW, pc.stride, pc.pad, in_ps or pc.Cin, out_ps or pc.Cout,
+                        (pc.Cout if res_ps is None else res_ps) if has_res else 0, pc.Kpad,
+                        int(act) | (MATH_BF16X3 if self.math == "bf16x3" else 0))
+
+    def _route(self, L, pc, d, stream, kind="conv", has_res=False, pre=False, splitk=False, splitk_n=0, aligned=False):
+        """How one layer launch goes out: the only place that decides it.  ``d`` is the layer's descriptor (:meth:`_desc`); the flags
+        of the route (fp64 accumulation, in-kernel summation blocks) are OR'ed into ``d.act``.  ``kind`` "conv": a launch of
+        :meth:`conv`; "group": may the job join a grouped launch of :meth:`conv_group` (entry "group", ``cls`` its kernel class) or does
+        it take :meth:`conv` (entry "conv"); "dual": the flags of :meth:`conv_dual`.  ``aligned``: input and output pointers are 16-byte
+        aligned.  The library's capture state is queried only for split launches (S > 1) and stream-K candidates."""
+        fp32 = self.math == "fp32"
+        acc64 = bool(self.acc64 and pc.acc64 and fp32 and pc.Cin != 4)
         if acc64:               # direct launch(es); a split keeps fp64 partial sums (per-sample head GEMMs, call-site constants)
             d.act |= ACC_F64
-            S = (L.hands_conv2d_splitk_factor(C.byref(d)) if (splitk and self.use_splitk) else 1)
-            if splitk_n > 1 and self.use_splitk:
-                S = splitk_n
-        rp = ptr(res, res_off) if res is not None else None
-        if (not acc64 and self.winograd and self.winograd4 and pc.wino4 is not None and res is None and pre is None and S <= 1
-                and self.math == "fp32" and (ptr(x, x_off) | ptr(out, out_off)) % 16 == 0
-                and L.hands_conv3x3_winograd4_supported(C.byref(d))):
-            if hook is not None:
-                self.last_wino_macs = L.hands_conv3x3_winograd4_executed_macs(C.byref(d))
-                hook("begin", pc, B * Ho * Wo, stream, False, "conv_wino4_f32_kernel")
-            check(L.hands_conv3x3_winograd4_f32(C.byref(d), ptr(x, x_off), ptr(pc.wino4), ptr(pc.bias), ptr(out, out_off), stream),
-                  "hands_conv3x3_winograd4_f32")
-            if hook is not None:
-                hook("end", pc, B * Ho * Wo, stream, False, "conv_wino4_f32_kernel")
-            return Ho, Wo
-        if (not acc64 and self.winograd and pc.wino is not None and res is None and pre is None and S <= 1 and self.math == "fp32"
-                and (ptr(x, x_off) | ptr(out, out_off)) % 16 == 0        # its accesses are 16 bytes wide
-                and L.hands_conv3x3_winograd_supported(C.byref(d))):
-            if hook is not None:
-                self.last_wino_macs = L.hands_conv3x3_winograd_executed_macs(C.byref(d))   # what the matrix cores execute
-                hook("begin", pc, B * Ho * Wo, stream, False, "conv_wino_f32_kernel")
-            check(L.hands_conv3x3_winograd_f32(C.byref(d), ptr(x, x_off), ptr(pc.wino), ptr(pc.bias), ptr(out, out_off), stream),
-                  "hands_conv3x3_winograd_f32")
-            if hook is not None:
-                hook("end", pc, B * Ho * Wo, stream, False, "conv_wino_f32_kernel")
-            return Ho, Wo
+        if kind == "dual":
+            return _Route("dual", 1, 0, acc64, "conv_igemm_f32_kernel")
+        S = 1
+        if kind == "conv":
+            if self.use_splitk:
+                S = splitk_n if splitk_n > 1 else (L.hands_conv2d_splitk_factor(C.byref(d)) if splitk else 1)
+            if self.latency_mode and not acc64:
+                # small-batch serving: a layer with a handful of output tiles walks a K of 2304-4608 serially
+                # on a few CUs; cut K so that ~256 workgroups exist, at least 8 k-steps (128 floats) per slice
+                bm, bn = (256, 64) if pc.Cout <= 64 else (128, 128)
+                tiles = -(-(d.B * d.Ho * d.Wo) // bm) * -(-pc.Cout // bn)
+                if tiles <= 128:
+                    S = max(S, min(256 // tiles, pc.Kpad // 128, 32))
+            if not acc64 and self.winograd and not has_res and not pre and S <= 1 and fp32 and aligned:   # 16-byte accesses
+                if self.winograd4 and pc.wino4 is not None and L.hands_conv3x3_winograd4_supported(C.byref(d)):
+                    return _Route("wino4", S, 0, False, "conv_wino4_f32_kernel")
+                if pc.wino is not None and L.hands_conv3x3_winograd_supported(C.byref(d)):
+                    return _Route("wino", S, 0, False, "conv_wino_f32_kernel")
+        # blocked summation (not the Winograd launches above: their chains are Cin long)
         limit = self.chain_limit if pc.sum_block < 0 else (pc.sum_block if self.chain_limit else 0)   # per-layer override of the block
-        if (limit and not acc64 and self.math == "fp32" and (self.chain_in_kernel or self.use_splitk)
+        sum_block = 0
+        if (limit and not acc64 and fp32 and (self.chain_in_kernel or self.use_splitk)
                 and pc.Kpad >= max(2 * limit, self.chain_min_k)
-                and (not self.chain_max_pix or Ho * Wo <= self.chain_max_pix)
-                and not (self.chain_skip_tokens and H * W == 1 and B >= 4096)):
-            # blocked summation (not the Winograd launches above: their chains are Cin long)
-            self.last_sum_block = limit
+                and (not self.chain_max_pix or d.Ho * d.Wo <= self.chain_max_pix)
+                and not (self.chain_skip_tokens and d.H * d.W == 1 and d.B >= 4096)):
+            sum_block = limit
             if self.chain_in_kernel:
                 if limit not in _SUM_BLOCK:
                     raise ValueError(f"hands_amd: chain_in_kernel takes chain_limit 64 or 128, not {limit}")
                 d.act |= _SUM_BLOCK[limit]
             else:
                 S = max(S, min(pc.Kpad // limit, 32))
-        if pre is not None:
-            # pointwise layer behind an eval BatchNorm -> LeakyReLU (pre = (scale, shift) device vectors): the affine +
-            # activation is applied to the operand on its way into LDS (hands_conv2d_nhwc_pre_f32)
-            kname = "conv_igemm_splitk_f32_kernel" if S > 1 else "conv_igemm_f32_kernel"
-            if hook is not None:
-                hook("begin", pc, B * Ho * Wo, stream, res is not None, kname)
-            ws = self._workspace(L, x.device, stream, L.hands_conv2d_workspace_floats(C.byref(d), S)) if S > 1 else None
-            check(L.hands_conv2d_nhwc_pre_f32(C.byref(d), ptr(x, x_off), ptr(pre[0]), ptr(pre[1]), ptr(pc.w), ptr(pc.bias), rp,
-                                              ptr(out, out_off), S, ptr(ws), ws.numel() if ws is not None else 0, stream),
-                  "hands_conv2d_nhwc_pre_f32")
-            if hook is not None:
-                hook("end", pc, B * Ho * Wo, stream, res is not None, kname)
-            return Ho, Wo
-        use_sk = S <= 1 and not acc64 and self.math == "fp32" and ((not self.overlap) if self.stream_k == "auto" else self.stream_k) and \
-            not (d.act & (_SUM_BLOCK[64] | _SUM_BLOCK[128])) and \
-            L.hands_conv2d_streamk_grid(C.byref(d)) > 0 and not self._capturing(L, stream)
+        if kind == "group":     # no fp64 and not the split-K form of the blocks; the library knows the kernel class
+            groupable = not acc64 and (self.chain_in_kernel or not limit)
+            cls = L.hands_conv2d_group_class(C.byref(d), int(pre)) if groupable else -1
+            return _Route("group" if cls >= 0 else "conv", S, sum_block, acc64, "conv_igemm_group_f32_kernel", cls=cls)
+        if S > 1:               # the workspace table, and whether the last slice may reduce, depend on the capture state
+            capturing = self._capturing(L, stream)
+            entry = "pre" if pre else ("splitk_fused" if self.fuse_splitk_reduce and not capturing else "splitk")
+            return _Route(entry, S, sum_block, acc64, "conv_igemm_splitk_f32_kernel", capturing)
+        if pre:
+            return _Route("pre", S, sum_block, acc64, "conv_igemm_f32_kernel")
         # (a blocked launch keeps the plain kernel: stream-K continues ONE chain across workgroups)
         # (not under hipGraph capture: the zero-filled workspace of a new stream cannot be set up inside one)
-        kname = "conv_igemm_splitk_f32_kernel" if S > 1 else ("conv_igemm_sk_f32_kernel" if use_sk else "conv_igemm_f32_kernel")
+        if (not sum_block and not acc64 and fp32 and ((not self.overlap) if self.stream_k == "auto" else self.stream_k)
+                and L.hands_conv2d_streamk_grid(C.byref(d)) > 0 and not self._capturing(L, stream)):
+            return _Route("streamk", S, 0, False, "conv_igemm_sk_f32_kernel")
+        return _Route("plain", S, sum_block, acc64, "conv_igemm_f32_kernel")
+
+    def _launch(self, kernel, pc, npix, stream, has_res, fn, *args):
+        """One library launch bracketed by the profiling hook (the same arguments on "begin" and "end")."""
+        hook = self.hook
         if hook is not None:
-            hook("begin", pc, B * Ho * Wo, stream, res is not None, kname)
-        if S > 1:     # latency-bound GEMM: deterministic split-K with a per-stream workspace
-            ws = self._workspace(L, x.device, stream, L.hands_conv2d_workspace_floats(C.byref(d), S))
-            ctr = self._counters(L, x.device, stream) if self.fuse_splitk_reduce else None
-            if ctr is not None:       # the last slice of a tile reduces it: no second launch (same bits)
-                check(L.hands_conv2d_nhwc_splitk_fused_f32(C.byref(d), ptr(x, x_off), ptr(pc.w), ptr(pc.bias), rp, ptr(out, out_off),
-                                                           S, ptr(ws), ws.numel(), ptr(ctr), ctr.numel(), stream),
-                      "hands_conv2d_nhwc_splitk_fused_f32")
-            else:
-                check(L.hands_conv2d_nhwc_splitk_n_f32(C.byref(d), ptr(x, x_off), ptr(pc.w), ptr(pc.bias), rp, ptr(out, out_off),
-                                                       S, ptr(ws), ws.numel(), stream), "hands_conv2d_nhwc_splitk_n_f32")
-        elif use_sk:
+            hook("begin", pc, npix, stream, has_res, kernel)
+        check(fn(*args), fn.__name__)
+        if hook is not None:
+            hook("end", pc, npix, stream, has_res, kernel)
+
+    def conv(self, L, pc, x, B, H, W, out, relu, stream, res=None, in_ps=None, out_ps=None, res_ps=None,
+             x_off=0, out_off=0, res_off=0, splitk=False, splitk_n=0, pre=None):
+        """One convolution / linear layer.  ``splitk=True`` marks rows that are per-SAMPLE (head MLPs): only
+        there may the library cut K by its own (layer-only) policy -- token / pixel GEMMs would cross the
+        library's row threshold between batch sizes and lose bit-reproducibility.  ``splitk_n`` is a
+        call-site constant slice count (summation order independent of the batch size).  ``pre = (scale, shift)``: a
+        pointwise layer behind an eval BatchNorm -> LeakyReLU, applied to the operand on its way into LDS."""
+        d = self._desc(pc, B, H, W, relu, in_ps, out_ps, res_ps, res is not None)
+        xp, op, wp, bp = ptr(x, x_off), ptr(out, out_off), ptr(pc.w), ptr(pc.bias)
+        rp = ptr(res, res_off) if res is not None else None
+        r = self._route(L, pc, d, stream, "conv", res is not None, pre is not None, splitk, splitk_n, (xp | op) % 16 == 0)
+        self.last_sum_block, self.last_acc64 = r.sum_block, r.acc64
+        dp = C.byref(d)
+        if r.entry == "wino4":
+            if self.hook is not None:
+                self.last_wino_macs = L.hands_conv3x3_winograd4_executed_macs(dp)
+            fn, args = L.hands_conv3x3_winograd4_f32, (dp, xp, ptr(pc.wino4), bp, op, stream)
+        elif r.entry == "wino":
+            if self.hook is not None:
+                self.last_wino_macs = L.hands_conv3x3_winograd_executed_macs(dp)   # what the matrix cores execute
+            fn, args = L.hands_conv3x3_winograd_f32, (dp, xp, ptr(pc.wino), bp, op, stream)
+        elif r.entry == "streamk":
             key = (x.device, stream)
             sk = self._sk_ws.get(key)
             if sk is None:
@@ -253,15 +254,21 @@ class ConvEngine:
                 sk = self._sk_ws[key] = [torch.zeros(nbytes // 4, dtype=torch.int32, device=x.device), 0]
                 torch.cuda.current_stream(x.device).synchronize()     # zero-fill done before a side stream uses it
             sk[1] = sk[1] % 0x7FFFFFF0 + 1
-            check(L.hands_conv2d_nhwc_streamk_f32(C.byref(d), ptr(x, x_off), ptr(pc.w), ptr(pc.bias), rp, ptr(out, out_off),
-                                                  ptr(sk[0]), sk[0].numel() * 4, sk[1], stream),
-                  "hands_conv2d_nhwc_streamk_f32")
-        else:
-            check(L.hands_conv2d_nhwc_f32(C.byref(d), ptr(x, x_off), ptr(pc.w), ptr(pc.bias), rp, ptr(out, out_off),
-                                          stream), "hands_conv2d_nhwc_f32")
-        if hook is not None:
-            hook("end", pc, B * Ho * Wo, stream, res is not None, kname)
-        return Ho, Wo
+            fn, args = L.hands_conv2d_nhwc_streamk_f32, (dp, xp, wp, bp, rp, op, ptr(sk[0]), sk[0].numel() * 4, sk[1], stream)
+        elif r.entry == "plain":
+            fn, args = L.hands_conv2d_nhwc_f32, (dp, xp, wp, bp, rp, op, stream)
+        else:   # pre / split-K: a deterministic S-slice launch with a per-stream workspace when S > 1
+            ws = self._workspace(x.device, stream, L.hands_conv2d_workspace_floats(dp, r.S), r.capturing) if r.S > 1 else None
+            wsp, wsn = (ptr(ws), ws.numel()) if ws is not None else (None, 0)
+            if r.entry == "pre":
+                fn, args = L.hands_conv2d_nhwc_pre_f32, (dp, xp, ptr(pre[0]), ptr(pre[1]), wp, bp, rp, op, r.S, wsp, wsn, stream)
+            elif r.entry == "splitk_fused":   # the last slice of a tile reduces it: no second launch (same bits)
+                ctr = self._counters(L, x.device, stream)   # (_route saw no capture: never None here)
+                fn, args = L.hands_conv2d_nhwc_splitk_fused_f32, (dp, xp, wp, bp, rp, op, r.S, wsp, wsn, ptr(ctr), ctr.numel(), stream)
+            else:
+                fn, args = L.hands_conv2d_nhwc_splitk_n_f32, (dp, xp, wp, bp, rp, op, r.S, wsp, wsn, stream)
+        self._launch(r.kernel, pc, B * d.Ho * d.Wo, stream, res is not None, fn, *args)
+        return d.Ho, d.Wo
 
     def conv_group(self, L, jobs, stream):
         """Independent layers that may run concurrently: ``jobs`` is a list of dicts with the arguments of :meth:`conv` (``pc, x, B,
@@ -277,38 +284,14 @@ class ConvEngine:
             return
         classes = {}
         for j in jobs:
-            pc, B, H, W = j["pc"], j["B"], j["H"], j["W"]
-            res, pre = j.get("res"), j.get("pre")
-            Ho = (H + 2 * pc.pad - pc.KH) // pc.stride + 1
-            Wo = (W + 2 * pc.pad - pc.KW) // pc.stride + 1
-            d = ConvDesc(B, H, W, pc.Cin, Ho, Wo, pc.Cout, pc.KH, pc.KW, pc.stride, pc.pad, j.get("in_ps") or pc.Cin,
-                         j.get("out_ps") or pc.Cout, (pc.Cout if j.get("res_ps") is None else j["res_ps"]) if res is not None else 0,
-                         pc.Kpad, int(j.get("relu", 0)))
-            cls = -1
-            if not (self.acc64 and pc.acc64 and pc.Cin != 4):
-                limit = self.chain_limit if pc.sum_block < 0 else (pc.sum_block if self.chain_limit else 0)
-                blocked = bool(limit and self.chain_in_kernel and pc.Kpad >= max(2 * limit, self.chain_min_k)
-                               and (not self.chain_max_pix or Ho * Wo <= self.chain_max_pix)
-                               and not (self.chain_skip_tokens and H * W == 1 and B >= 4096))
-                if limit and not self.chain_in_kernel:
-                    blocked = None                     # the split-K form of the blocks: not a grouped launch
-                if blocked is not None:
-                    if blocked:
-                        if limit not in _SUM_BLOCK:
-                            raise ValueError(f"hands_amd: chain_in_kernel takes chain_limit 64 or 128, not {limit}")
-                        d.act |= _SUM_BLOCK[limit]
-                    cls = L.hands_conv2d_group_class(C.byref(d), 1 if pre is not None else 0)
-                    j["_blocked"] = limit if blocked else 0
-            j["_d"], j["_npix"] = d, B * Ho * Wo
-            classes.setdefault(cls, []).append(j)
-        hook = self.hook
+            pc = j["pc"]
+            d = self._desc(pc, j["B"], j["H"], j["W"], j.get("relu", 0), j.get("in_ps"), j.get("out_ps"), j.get("res_ps"),
+                           j.get("res") is not None)
+            r = self._route(L, pc, d, stream, "group", pre=j.get("pre") is not None)
+            j["_d"], j["_npix"], j["_sum_block"] = d, j["B"] * d.Ho * d.Wo, r.sum_block
+            classes.setdefault(r.cls, []).append(j)
         for cls, members in classes.items():
-            if cls < 0 or len(members) < 2:
-                for j in members:
-                    single(j)
-                continue
-            for i in range(0, len(members), 8):
-                chunk = members[i:i + 8]
+            for chunk in ([members[i:i + 8] for i in range(0, len(members), 8)] if cls >= 0 else [[j] for j in members]):
                 if len(chunk) == 1:
                     single(chunk[0])
                     continue
@@ -318,52 +301,48 @@ class ConvEngine:
                     arr[k] = ConvJob(C.pointer(j["_d"]), ptr(j["x"], j.get("x_off", 0)), ptr(pc.w), ptr(pc.bias),
                                      ptr(res, j.get("res_off", 0)) if res is not None else None, ptr(j["out"], j.get("out_off", 0)),
                                      ptr(pre[0]) if pre is not None else None, ptr(pre[1]) if pre is not None else None)
-                self.last_sum_block, self.last_acc64 = chunk[0]["_blocked"], False
-                if hook is not None:
-                    gp = _GroupPC(chunk)
-                    hook("begin", gp, gp.npix, stream, any(j.get("res") is not None for j in chunk), "conv_igemm_group_f32_kernel")
-                check(L.hands_conv2d_group_f32(arr, len(chunk), stream), "hands_conv2d_group_f32")
-                if hook is not None:
-                    hook("end", gp, gp.npix, stream, False, "conv_igemm_group_f32_kernel")
+                self.last_sum_block, self.last_acc64 = chunk[0]["_sum_block"], False
+                gp = _GroupPC(chunk) if self.hook is not None else None
+                self._launch("conv_igemm_group_f32_kernel", gp, gp.npix if gp else 0, stream,
+                             any(j.get("res") is not None for j in chunk), L.hands_conv2d_group_f32, arr, len(chunk), stream)
 
     def conv_dual(self, L, pc, split, x, x2, B, Ho, Wo, H2, W2, out, stream, act=1, out_off=0):
         """act(conv3(x) + downsample(x2)) (resnet.py:146-154) with the identity never materialised."""
         K0, K1, stride2 = split
         d = ConvDesc(B, Ho, Wo, K0, Ho, Wo, pc.Cout, 1, 1, 1, 0, K0, pc.Cout, 0, pc.Kpad,
                      int(act) | (MATH_BF16X3 if self.math == "bf16x3" else 0))
-        hook = self.hook
-        if hook is not None:
-            hook("begin", pc, B * Ho * Wo, stream, False, "conv_igemm_f32_kernel")
-        check(L.hands_conv1x1_dual_nhwc_f32(C.byref(d), ptr(x), ptr(x2), K1, H2, W2, stride2, K1, ptr(pc.w), ptr(pc.bias),
-                                            ptr(out, out_off), stream), "hands_conv1x1_dual_nhwc_f32")
-        if hook is not None:
-            hook("end", pc, B * Ho * Wo, stream, False, "conv_igemm_f32_kernel")
+        if self._route(L, pc, d, stream, "dual").acc64:
+            raise ValueError("hands_amd: conv_dual has no fp64 accumulation (hands_conv1x1_dual_nhwc_f32): a layer marked acc64 "
+                             "takes its conv3 and downsample as separate launches")
+        self._launch("conv_igemm_f32_kernel", pc, B * Ho * Wo, stream, False, L.hands_conv1x1_dual_nhwc_f32,
+                     C.byref(d), ptr(x), ptr(x2), K1, H2, W2, stride2, K1, ptr(pc.w), ptr(pc.bias), ptr(out, out_off), stream)
 
     def stem_pool(self, L, pc, x4, x_off, out, B, H, W, act, stream):
         """conv 7x7/2 + folded BN + act + max-pool 3x3/2 in one kernel (resnet.py:264-268); the conv map
         (B, Hc, Wc, 64) never reaches HBM.  Returns the conv map size (Hc, Wc)."""
         Hc, Wc = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-        hook = self.hook
-        if hook is not None:
-            hook("begin", pc, B * Hc * Wc, stream, False, "stem_pool_kernel")
-        check(L.hands_stem_conv_maxpool_nhwc_f32(ptr(x4, x_off), ptr(pc.w), ptr(pc.bias), ptr(out), B, H, W, int(act), stream),
-              "hands_stem_conv_maxpool_nhwc_f32")
-        if hook is not None:
-            hook("end", pc, B * Hc * Wc, stream, False, "stem_pool_kernel")
+        self._launch("stem_pool_kernel", pc, B * Hc * Wc, stream, False, L.hands_stem_conv_maxpool_nhwc_f32,
+                     ptr(x4, x_off), ptr(pc.w), ptr(pc.bias), ptr(out), B, H, W, int(act), stream)
         return Hc, Wc
 
     def stem_pool_nchw(self, L, pc, x, x_off, out, out_off, B, H, W, act, stream):
         """The same stem reading the NCHW image in place (hands_stem_conv_maxpool_nchw_f32): K = 3 planes x 52 =
         160 instead of 208, and no NHWC4 copy of the input.  ``pc`` is the planar packing (k = plane * 52 + tap)."""
         Hc, Wc = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-        hook = self.hook
-        if hook is not None:
-            hook("begin", pc, B * Hc * Wc, stream, False, "stem_pool_planar_kernel")
-        check(L.hands_stem_conv_maxpool_nchw_f32(ptr(x, x_off), ptr(pc.w), ptr(pc.bias), ptr(out, out_off), B, H, W, int(act),
-                                                 stream), "hands_stem_conv_maxpool_nchw_f32")
-        if hook is not None:
-            hook("end", pc, B * Hc * Wc, stream, False, "stem_pool_planar_kernel")
+        self._launch("stem_pool_planar_kernel", pc, B * Hc * Wc, stream, False, L.hands_stem_conv_maxpool_nchw_f32,
+                     ptr(x, x_off), ptr(pc.w), ptr(pc.bias), ptr(out, out_off), B, H, W, int(act), stream)
         return Hc, Wc
+
+
+class _Route(NamedTuple):
+    """What :meth:`ConvEngine._route` decided for one launch."""
+    entry: str                # wino4 | wino | pre | splitk_fused | splitk | streamk | plain | dual; group | conv (kind "group")
+    S: int                    # K slices
+    sum_block: int            # blocked summation (either form): the block in floats; 0 = one chain
+    acc64: bool
+    kernel: str               # the kernel name the hook reports
+    capturing: bool = False   # the launch stream is being captured (known for S > 1)
+    cls: int = -1             # kind "group": hands_conv2d_group_class
 
 
 class _GroupPC:

@@ -87,8 +87,9 @@ typedef struct hands_conv_desc {
  * split on the fly into three bf16 planes whose sum is the fp32 value exactly, and the products b_i * b_j with
  * i + j <= 2 run on the bf16 matrix pipe with fp32 accumulation (dropped terms <= 2^-24 of a product).  A separately
  * reported mode: results are fp32-grade but NOT bit-identical to the fp32 chain.  Honoured by
- * hands_conv2d_nhwc_f32 and hands_conv1x1_dual_nhwc_f32 (not the RGB0 stem); the split-K / stream-K entries
- * ignore it (fp32). */
+ * hands_conv2d_nhwc_f32 and hands_conv1x1_dual_nhwc_f32 (not the RGB0 stem); the stream-K entry hands such a descriptor to
+ * hands_conv2d_nhwc_f32 (honoured); the split-K entries run a launch they really split as exact fp32 (S <= 1 or a too small
+ * workspace: the hands_conv2d_nhwc_f32 call, honoured); hands_conv2d_nhwc_pre_f32 rejects it (HANDS_EINVAL). */
 #define HANDS_MATH_BF16X3 0x100
 /* Blocked fp32 summation, OR'ed into desc.act (round 5): the k-ordered FMA chain of every output is cut into blocks of 128 /
  * 64 floats (8 / 4 k-steps); a block's sum is added to a second accumulator set in block order -- no fp32 accumulation chain
@@ -105,7 +106,8 @@ typedef struct hands_conv_desc {
  * (handoccnet_light's heat-map head, hand_head.py:75-94,266-280), not for throughput.  Batch-size invariant and deterministic.
  * Honoured by hands_conv2d_nhwc_f32, hands_conv2d_nhwc_pre_f32 and the split-K entries (the partial sums are fp64 there:
  * hands_conv2d_workspace_floats doubles, the workspace must be 8-byte aligned); the stream-K entry runs it as ONE plain launch;
- * not for the RGB0 stem (Cin == 4) and not together with the flags above (HANDS_EINVAL). */
+ * hands_conv1x1_dual_nhwc_f32 has no fp64 form and rejects it; not for the RGB0 stem (Cin == 4) and not together with the flags
+ * above (HANDS_EINVAL). */
 #define HANDS_ACC_F64 0x800
 
 int hands_conv2d_nhwc_f32(const hands_conv_desc* d, const float* in, const float* w_packed,
@@ -182,7 +184,8 @@ int hands_conv2d_nhwc_splitk_n_f32(const hands_conv_desc* d, const float* in, co
  * zero by every call (one array per stream: concurrent launches must not share it).  The slice of a tile that arrives last adds
  * the partial sums in ascending slice order and applies bias / residual / activation -- the output bits of the two-launch form,
  * one launch.  n_counters below the launch's tile count (ceil(M / 128) * ceil(Cout / 128), or ceil(M / 256) for Cout <= 64):
- * falls back to the two launches. */
+ * falls back to the two launches.  `out` may alias `residual` (an in-place residual update), never `in`: the last slice of a tile
+ * writes `out` while slices of other tiles still read `in`. */
 int hands_conv2d_nhwc_splitk_fused_f32(const hands_conv_desc* d, const float* in, const float* w_packed,
                                        const float* bias, const float* residual, float* out, int S,
                                        float* workspace, long long workspace_floats, int* counters,

@@ -230,6 +230,8 @@ def test_bad_descriptors_are_rejected_without_a_gpu():
     assert L.hands_conv2d_nhwc_splitk_n_f32(ctypes.byref(d5), 16, 16, 16, None, 16, 2, 16, 1 << 20, None) == 10001
     d = _lib.ConvDesc(70000, 224, 224, 16, 224, 224, 64, 1, 1, 1, 0, 16, 64, 0, 16, 0)   # > 2^31 elements
     assert L.hands_conv2d_nhwc_f32(ctypes.byref(d), 16, 16, 16, None, 16, None) == 10001
+    d = _lib.ConvDesc(1, 7, 7, 16, 7, 7, 64, 1, 1, 1, 0, 16, 64, 0, 32, 0x800)   # the dual entry has no fp64 form (HANDS_ACC_F64)
+    assert L.hands_conv1x1_dual_nhwc_f32(ctypes.byref(d), 16, 16, 16, 7, 7, 1, 16, 16, 16, 16, None) == 10001
     with pytest.raises(RuntimeError):
         _lib.check(10001, "x")
 
