@@ -125,6 +125,7 @@ SIGNATURES = {
     "hands_unnormalize_kp2d_f32": [_P, _P, C.c_longlong, _F, _P],
     "hands_frontend_boxes_f32": [_P, _P, _I, _P, _I, _I, _I, C.c_double] + [_P] * 10 + [_P],
     "hands_warp_affine_cubic_norm_f32": [_P, _P, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _P],
+    "hands_render_silhouette_f32": [_P, _I, _I, _P, _I, _P, _I, _I, _F, _F, _I, _P, _P, _P, _P],
     # host-side packing (csrc/pack.cpp): HOST pointers
     "hands_pack_conv_dims": [_I, _I, _I, _I, _I, C.POINTER(PackedDims)],
     "hands_fold_bn_f32": [_I, C.c_longlong, _P, _P, _P, _P, _P, C.c_double, _P, _P],

@@ -188,9 +188,10 @@ class HAMER(EngineSwitches, nn.Module):
         # built: pos_enc 'center+corner_latent' (shipped) or None (no KPE: model.py:91-97,102-104), grasp head on or off
         # (model.py:59-72,136-143).  'dense_latent' cannot run in the reference either: PositionalEncoding.forward calls
         # compute_dense_pos_enc(angle, mask) without its `size` argument (hamer_light/pos_emb.py:41 vs :66) -> TypeError.  The
-        # renderer is not built
+        # renderer is a class of its own (hands_amd.MANORenderer), not a constructor switch
         if get("pos_enc") not in ("center+corner_latent", None) or get("use_render_seg_loss", False):
-            raise NotImplementedError("hands_amd.HAMER: pos_enc must be 'center+corner_latent' or None, renderer off")
+            raise NotImplementedError("hands_amd.HAMER: pos_enc must be 'center+corner_latent' or None, use_render_seg_loss off "
+                                      "(call hands_amd.MANORenderer on the output instead)")
         self.n_freq = int(get("n_freq_pos_enc", 4))
         self.vit_input_size = (256, 192)
         self.backbone = ViTParams()

@@ -89,7 +89,8 @@ class HandOccNet(EngineSwitches, nn.Module):
         # 'dense_latent' fails in the reference's own PositionalEncoding (hamer_light/pos_emb.py:41 calls compute_dense_pos_enc
         # without its `size` argument)
         if get("pos_enc") not in ("center+corner_latent", None) or get("use_render_seg_loss", False):
-            raise NotImplementedError("hands_amd.HandOccNet: pos_enc must be 'center+corner_latent' or None, renderer off")
+            raise NotImplementedError("hands_amd.HandOccNet: pos_enc must be 'center+corner_latent' or None, use_render_seg_loss off "
+                                      "(call hands_amd.MANORenderer on the output instead)")
         self.n_freq = int(get("n_freq_pos_enc", 4))
         self.input_size = (256, 256)
         self.pos_enc = get("pos_enc")

@@ -314,7 +314,7 @@ class HandsLight(EngineSwitches, nn.Module):
             f"pos_enc={pos_enc!r}": self.enc_mode is None,
             "tf_decoder": bool(get("tf_decoder", False)),
             "use_depth_loss with no_crops": self.use_depth_loss and self.no_crops,      # `depth_r` undefined in the reference (:308-310, 422)
-            "use_render_seg_loss": bool(get("use_render_seg_loss", False)),
+            "use_render_seg_loss (call hands_amd.MANORenderer on the output instead)": bool(get("use_render_seg_loss", False)),
             # the reference itself fails on these combinations (`features` / `feat_vec` undefined, model.py:191-201, 402-404;
             # center_head on a 4-D map, :428)
             "use_glb_feat=False with no_crops": not self.use_glb_feat and self.no_crops,

@@ -579,6 +579,25 @@ int hands_warp_affine_cubic_norm_f32(const float* src, const float* trans, float
                                      hands_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Soft-silhouette renderer of the predicted meshes (csrc/render.hip), forward only: MANORenderer / DiffRenderer,
+ * src/models/hands_light/renderer.py:112-207, called at hands_light/model.py:413-420 on mano.v3d.cam.{r,l}.  The reference
+ * delegates to pytorch3d (MeshRasterizer: blur_radius > 0, faces_per_pixel = 10, perspective_correct = False; then
+ * SoftSilhouetteShader), which is third party and absent: the kernel restates the published naive rasterize_meshes path and
+ * sigmoid_alpha_blend ("parity unpinned"; the semantics are written out in the header of csrc/render.hip).
+ *   verts (B, n_verts, 3) in the camera frame, hand b at verts + b * ld_verts (ld_verts >= 3 n_verts floats);
+ *   faces (n_faces, 3) int32, shared by the batch; a face with an index outside [0, n_verts) or a vertex at Z <= 0 is skipped
+ *   (the latter a stated deviation: pytorch3d projects such vertices through the camera centre);
+ *   K (B, 3, 3): only K00, K11, K02, K12 are read (no skew), in pixels of the S x S image;
+ *   pixel (r, c) samples the image point (c + 0.5, r + 0.5); sigma and blur_radius in squared NDC units
+ *   (the reference: 1e-5 and log(1/1e-6 - 1) * 1e-5); faces_per_pixel nearest candidates are blended, ties to the lower index.
+ *   mask (B, S, S) = alpha in [0, 1].  Optional (NULL = not written), from the same pass, over the faces that CONTAIN the pixel:
+ *   face_idx (B, S, S) int32, -1 where empty, and zbuf (B, S, S), the screen-space interpolated depth, 0 where empty.
+ * HANDS_EINVAL (nothing launched): faces_per_pixel outside [1, 10]; a vertex block that does not fit in LDS beside the face
+ * list (12 n_verts + 24 608 > 65 536 bytes, i.e. n_verts > 3410); sigma <= 0; blur_radius < 0; S outside [1, 16384].
+ * n_faces is unbounded: a tile whose face list overflows its LDS share is processed in chunks. */
+int hands_render_silhouette_f32(const float* verts, int ld_verts, int n_verts, const int32_t* faces, int n_faces, const float* K, int B, int S, float sigma, float blur_radius, int faces_per_pixel, float* mask, int32_t* face_idx, float* zbuf, hands_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * One-time HOST-side packing (csrc/pack.cpp): reference-layout parameters -> the layouts above.
  * Host pointers only, no GPU call, no allocation kept.  A host in any language packs a reference
  * checkpoint with these and uploads the results; hands_amd/packing.py is a thin ctypes wrapper.
