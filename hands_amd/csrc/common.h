@@ -11,3 +11,6 @@ static inline int hands_grid_1d(long long work, int block, int cap = 256 * 8) {
   if (g > cap) g = cap;
   return (int)g;
 }
+
+// vit_b.hip: the (T, head_dim) = (197, 64) launch behind hands_attention_f32 (transformer.hip)
+__attribute__((visibility("hidden"))) int hands_detail_attention_t197_d64(const float* qkv, float* out, int B, int heads, float scale, hipStream_t stream);

@@ -380,6 +380,9 @@ int hands_layernorm_f32(const float* x, const float* gamma, const float* beta, f
   else if (C == 1024)
     hipLaunchKernelGGL(layernorm_kernel<4>, grid, block, 0, (hipStream_t)stream, x, gamma, beta, out, addvec,
                        rows_per_vec, M, eps);
+  else if (C == 768)     // ViT-B/16 (hands_light, backbone='vit_b_16')
+    hipLaunchKernelGGL(layernorm_kernel<3>, grid, block, 0, (hipStream_t)stream, x, gamma, beta, out, addvec,
+                       rows_per_vec, M, eps);
   else if (C == 256)
     hipLaunchKernelGGL(layernorm_kernel<1>, grid, block, 0, (hipStream_t)stream, x, gamma, beta, out, addvec,
                        rows_per_vec, M, eps);
@@ -420,6 +423,9 @@ int hands_attention_f32(const float* qkv, float* out, int B, int T, int heads, i
     }
     hipLaunchKernelGGL((attention_kernel<12, 80>), dim3(heads, B), dim3(768), (attention_lds_bytes<12, 80>()), (hipStream_t)stream,
                        qkv, out, heads, scale);
+  } else if (T == 197 && head_dim == 64) {
+    // ViT-B/16 at 224x224 (196 patches + class token): attention_pad_kernel<13, 64, 197> of vit_b.hip
+    return hands_detail_attention_t197_d64(qkv, out, B, heads, scale, (hipStream_t)stream);
   } else {
     return HANDS_EINVAL;
   }

@@ -149,10 +149,15 @@ class ConvEngine:
             torch.cuda.current_stream(dev).synchronize()     # zero fill done before a side stream uses it
         return c
 
-    def _desc(self, pc, B, H, W, act, in_ps, out_ps, res_ps, has_res):
-        """The descriptor of one layer launch; act: bool or a HANDS_ACT_* code (the route adds its flags)."""
+    def _desc(self, pc, B, H, W, act, in_ps, out_ps, res_ps, has_res, out_hw=None):
+        """The descriptor of one layer launch; act: bool or a HANDS_ACT_* code (the route adds its flags).  ``out_hw``: compute only
+        the top-left (Ho, Wo) corner of the output map (the library takes any map not larger than the geometry's)."""
         Ho = (H + 2 * pc.pad - pc.KH) // pc.stride + 1
         Wo = (W + 2 * pc.pad - pc.KW) // pc.stride + 1
+        if out_hw is not None:
+            if not (0 < out_hw[0] <= Ho and 0 < out_hw[1] <= Wo):
+                raise ValueError(f"hands_amd: out_hw {tuple(out_hw)} is not inside the layer's {Ho} x {Wo} output map")
+            Ho, Wo = out_hw
         return ConvDesc(B, H, W, pc.Cin, Ho, Wo, pc.Cout, pc.KH, pc.KW, pc.stride, pc.pad, in_ps or pc.Cin, out_ps or pc.Cout,
                         (pc.Cout if res_ps is None else res_ps) if has_res else 0, pc.Kpad,
                         int(act) | (MATH_BF16X3 if self.math == "bf16x3" else 0))
@@ -226,13 +231,14 @@ class ConvEngine:
             hook("end", pc, npix, stream, has_res, kernel)
 
     def conv(self, L, pc, x, B, H, W, out, relu, stream, res=None, in_ps=None, out_ps=None, res_ps=None,
-             x_off=0, out_off=0, res_off=0, splitk=False, splitk_n=0, pre=None):
+             x_off=0, out_off=0, res_off=0, splitk=False, splitk_n=0, pre=None, out_hw=None):
         """One convolution / linear layer.  ``splitk=True`` marks rows that are per-SAMPLE (head MLPs): only
         there may the library cut K by its own (layer-only) policy -- token / pixel GEMMs would cross the
         library's row threshold between batch sizes and lose bit-reproducibility.  ``splitk_n`` is a
         call-site constant slice count (summation order independent of the batch size).  ``pre = (scale, shift)``: a
-        pointwise layer behind an eval BatchNorm -> LeakyReLU, applied to the operand on its way into LDS."""
-        d = self._desc(pc, B, H, W, relu, in_ps, out_ps, res_ps, res is not None)
+        pointwise layer behind an eval BatchNorm -> LeakyReLU, applied to the operand on its way into LDS.  ``out_hw``: see
+        :meth:`_desc`."""
+        d = self._desc(pc, B, H, W, relu, in_ps, out_ps, res_ps, res is not None, out_hw)
         xp, op, wp, bp = ptr(x, x_off), ptr(out, out_off), ptr(pc.w), ptr(pc.bias)
         rp = ptr(res, res_off) if res is not None else None
         r = self._route(L, pc, d, stream, "conv", res is not None, pre is not None, splitk, splitk_n, (xp | op) % 16 == 0)

@@ -19,16 +19,22 @@ statement of ``forward`` runs as a hand-written gfx950 kernel from ``libhands_hi
                                               hands_mano_pose_f32 -> blend GEMM -> hands_mano_skin_f32 is its cross-check)
     :401-404      grasp classifier            hands_grasp_input_f32, hands_conv2d_nhwc_f32 x4
 
-torch is used for parameter containers, device buffers and streams only.  Built configurations: resnet50,
+    :194-195,233-242,483-493  ViT-B/16 trunks (backbone='vit_b_16') hands_conv2d_nhwc_f32 (conv_proj 16x16/s16, qkv, out_proj +
+                                              residual, fc1 + GELU, fc2 + residual), hands_vit_tokens_f32 (class token + position
+                                              embedding), hands_layernorm_f32 (C = 768), hands_attention_f32 (197 tokens, 12 x 64),
+                                              hands_vit_tail_f32 (encoder.ln + AvgPool2d(2)), vit_conv as one folded 3x3 layer
+
+torch is used for parameter containers, device buffers and streams only.  Built configurations: backbones resnet50 and vit_b_16,
 tf_decoder=False with every pos_enc of model.py -- 'center+corner_latent' (shipped default), 'sinusoidal_cc', 'center', 'corner',
 'center+corner', 'dense', 'dense_latent', 'cam_conv', 'pcl', 'perspective_correction', None -- ``no_crops`` (arctic_light), the
 grasp head with / without the global feature vector or absent, ``separate_hands``, ``regress_center_corner``,
-``use_glb_feat=False``, ``use_depth_loss`` (the depth head); tf_decoder, the ViT backbone and the renderer raise
+``use_glb_feat=False``, ``use_depth_loss`` (the depth head); tf_decoder, backbone='resnet18' and the renderer switch raise
 ``NotImplementedError``.
 """
 from __future__ import annotations
 
 import ctypes as C
+import types
 
 import torch
 import torch.nn as nn
@@ -37,11 +43,14 @@ from . import _lib
 from ._lib import ManoConsts, ManoOut, ManoSide, check, ptr
 from .engine import DEFAULT_ENGINE, ConvEngine, EngineSwitches
 from .mano import ManoLayer, build_mano_asset
-from .packing import (HMR_VEC, PackedConv, fold_bn, hmr_state_columns, pack_conv, pack_conv1x1_dual,
+from .packing import (BN_EPS, HMR_VEC, PackedConv, fold_bn, hmr_state_columns, pack_conv, pack_conv1x1_dual,
                       pack_linear, pack_mano)
+from .vit_b16 import (VITB_DIM, VITB_GRID, VITB_HDIM, VITB_HEADS, VITB_LN_EPS, VITB_MLP, VITB_RES, VITB_TOKENS, ViTB16Params,
+                      vit_conv_params)
 from .xdict import prefix_dict, stream_xdict, xdict
 
 RESNET50_LAYERS = (3, 4, 6, 3)
+BACKBONES = ("resnet50", "vit_b_16")      # model.py:19-31 also names resnet18: not built
 
 
 # --------------------------------------------------------------------------------------------------
@@ -280,14 +289,15 @@ class HandsLight(EngineSwitches, nn.Module):
         # falls back to F(2x2) without repacking.
         self.winograd4_stages = (1, 2, 3, 4)
         self.engine.winograd4 = True
-        self.trunk_chunks = (1, 2)    # (global, hand) trunk jobs, one HIP stream each
+        self.trunk_chunks = (1, 2)    # (global, hand) trunk jobs, one HIP stream each (ViT-B/16: (1, 1), set below)
         self.async_tail = True        # tail of the forward on its own stream, joined at first use of the result
         self._calls = 0
         args = args if args is not None else DEFAULT_ARGS
         get = (lambda k, d=None: args.get(k, d)) if hasattr(args, "get") else (lambda k, d=None: getattr(args, k, d))
         self.args = args
-        if backbone != "resnet50":
-            raise NotImplementedError("hands_amd.HandsLight: only backbone='resnet50' is built")
+        if backbone not in BACKBONES:
+            raise NotImplementedError(f"hands_amd.HandsLight: backbone={backbone!r} is not built (built: {BACKBONES})")
+        self.backbone_name = backbone
         # Configuration switches (model.py:33-157).  Built: the latent KPE ('center+corner_latent', and 'sinusoidal_cc' whose
         # forward is the same code, model.py:258-271 / 288-304), the image-level encodings 'center' / 'corner' /
         # 'center+corner' (extra input channels of the hand trunk's conv1, model.py:60-77, 203-218), no encoding (None),
@@ -320,6 +330,9 @@ class HandsLight(EngineSwitches, nn.Module):
             "use_glb_feat=False with no_crops": not self.use_glb_feat and self.no_crops,
             "use_glb_feat=False with use_glb_feat_w_grasp": (not self.use_glb_feat and self.use_grasp_loss and self.use_glb_feat_w_grasp),
             "regress_center_corner with no_crops": self.regress_center_corner and self.no_crops,
+            # (model.py:72-73 hands conv_proj's bias TENSOR to nn.Conv2d(bias=...): "Boolean value of Tensor ... is ambiguous")
+            "separate_hands with a widened conv_proj on vit_b_16": (backbone == "vit_b_16" and self.separate_hands
+                                                                    and self.enc_mode in ("image", "dense")),
         }
         bad = [k for k, v in unsupported.items() if v]
         if bad:
@@ -327,15 +340,27 @@ class HandsLight(EngineSwitches, nn.Module):
         self.n_freq = int(get("n_freq_pos_enc", 4))
         feat_dim = 2048
         self.feat_dim = feat_dim
-        self.backbone = ResNet50Params()      # (the reference builds it even with use_glb_feat = False: same state_dict keys)
+        vit = backbone == "vit_b_16"
+        Trunk = ViTB16Params if vit else ResNet50Params
+        self.backbone = Trunk()               # (the reference builds it even with use_glb_feat = False: same state_dict keys)
+        if vit:                               # model.py:25-29: the tail that turns the 14x14 tokens into (2048, 7, 7) features
+            self.vit_conv = vit_conv_params()
+            # the 2 bz crops stay ONE job: its GEMMs have 394 bz rows (fc1: x 3072 columns), enough tiles to fill the chip alone
+            self.trunk_chunks = (1, 1)
         # model.py:60-77: conv1 of the hand trunk takes the image-level encoding as extra input channels
         self.enc_channels = ({1: 4, 2: 16, 3: 20}[IMAGE_ENC[pos_enc]] * self.n_freq if self.enc_mode == "image" else
                              4 * self.n_freq if self.enc_mode == "dense" else 0)
+        # (ViT: `conv_proj` is what is widened, model.py:45-58, 71-78; every hand trunk has its own vit_conv)
         if self.separate_hands:
-            self.hand_backbone_r = ResNet50Params(3 + self.enc_channels)
-            self.hand_backbone_l = ResNet50Params(3 + self.enc_channels)
+            self.hand_backbone_r = Trunk(3 + self.enc_channels)
+            self.hand_backbone_l = Trunk(3 + self.enc_channels)
+            if vit:
+                self.hand_backbone_r_vit_conv = vit_conv_params()
+                self.hand_backbone_l_vit_conv = vit_conv_params()
         else:
-            self.hand_backbone = ResNet50Params(3 + self.enc_channels)
+            self.hand_backbone = Trunk(3 + self.enc_channels)
+            if vit:
+                self.hand_backbone_vit_conv = vit_conv_params()
         self.head_r = HandHMR(feat_dim, True, 3)
         self.head_l = HandHMR(feat_dim, False, 3)
         self.latent_channels = (5 * 4 * self.n_freq if self.enc_mode == "latent" else 4 * self.n_freq if pos_enc == "dense_latent" else
@@ -426,6 +451,51 @@ class HandsLight(EngineSwitches, nn.Module):
         return P
 
     @torch.no_grad()
+    def _pack_vit_trunk(self, net: ViTB16Params, tail: nn.Sequential, dev):
+        """ViT-B/16 + vit_conv in kernel layout (once per load_state_dict, like the ResNet trunk): the patch embedding as a
+        16x16 / stride 16 convolution on NHWC4 (or on the padded NHWC map of the widened form), the four linears of every block
+        through pack_linear, and vit_conv's Conv2d bias + eval BatchNorm2d folded in fp64 into one 3x3 / pad 1 layer."""
+        cpu = lambda t: t.detach().cpu()
+        lin = lambda w, b: pack_linear(cpu(w), cpu(b), dev)
+        ln = lambda m: (cpu(m.weight).float().contiguous().to(dev), cpu(m.bias).float().contiguous().to(dev))
+        P = {"vit": True}
+        w, b = cpu(net.conv_proj.weight), cpu(net.conv_proj.bias)
+        if w.shape[1] == 3:
+            P["patch"] = pack_conv(w, b, 16, 0, dev, cin_pad_to=4)
+        else:
+            # widened conv_proj (image-level encodings) on the padded NHWC map.  The general implicit GEMM takes kernels of at most
+            # 15 x 15 taps when Cin != 4, so the 16 x 16 / stride 16 layer runs as TWO launches on a strip view of the same memory:
+            # 16 image rows x 224 pixels x Cp channels are 16 rows x 14 patches x (16 Cp) channels, i.e. every strip of 16 rows is an
+            # "image" (H 16, W 14, C 16 Cp) on which the patch embedding is a KH 16 x KW 1 kernel with one output row.  Its upper
+            # and lower 8 rows are one launch each (k order (kh, kw, c) is the same in both views); the second adds the first
+            # through the residual epilogue.  No copy of the map is made.
+            Cp = (w.shape[1] + 15) // 16 * 16
+            P["stem_wide"] = types.SimpleNamespace(Cin=Cp)       # what the callers ask: the padded channel count of the map
+            P["patch_halves"] = []
+            for h0 in (0, 8):
+                pc = pack_conv(w[:, :, h0:h0 + 8, :], b if h0 == 0 else None, 1, 0, dev, cin_pad_to=Cp)
+                pc.Cin, pc.KH, pc.KW = 16 * Cp, 8, 1             # the strip view of the same packed weight
+                P["patch_halves"].append(pc)
+        P["cls"] = cpu(net.class_token).float().reshape(VITB_DIM).contiguous().to(dev)
+        P["pos"] = cpu(net.encoder.pos_embedding).float().reshape(VITB_TOKENS, VITB_DIM).contiguous().to(dev)
+        P["blocks"] = []
+        for blk in net.encoder.layers:
+            at = blk.self_attention
+            P["blocks"].append({"n1": ln(blk.ln_1), "qkv": lin(at.in_proj_weight, at.in_proj_bias),
+                                "proj": lin(at.out_proj.weight, at.out_proj.bias), "n2": ln(blk.ln_2),
+                                "fc1": lin(blk.mlp[0].weight, blk.mlp[0].bias), "fc2": lin(blk.mlp[3].weight, blk.mlp[3].bias)})
+        P["last"] = ln(net.encoder.ln)
+        # vit_conv (utils.py:27-34): y = relu(bn(conv(x) + cb)) = relu(conv'(x) + b'), w' = w g / sqrt(var + eps),
+        # b' = (cb - mean) g / sqrt(var + eps) + beta, all in fp64 and rounded to fp32 once by pack_conv.  Winograd F(2x2,3x3)
+        # weights only: at 1.4 of the trunk's 36 GFLOP the F(4x4) form has nothing to win and its larger rounding error to lose.
+        conv, bn = tail[1], tail[2]
+        sc = cpu(bn.weight).double() / torch.sqrt(cpu(bn.running_var).double() + BN_EPS)
+        wf = cpu(conv.weight).double() * sc[:, None, None, None]
+        bf = (cpu(conv.bias).double() - cpu(bn.running_mean).double()) * sc + cpu(bn.bias).double()
+        P["vit_conv"] = pack_conv(wf, bf, 1, 1, dev)
+        return P
+
+    @torch.no_grad()
     def _pack_head(self, head: HandHMR, dev):
         cpu = lambda t: t.detach().cpu()
         F = self.feat_dim
@@ -450,14 +520,18 @@ class HandsLight(EngineSwitches, nn.Module):
         cpu = lambda t: t.detach().cpu()
         F = self.feat_dim
         P = {"head_r": self._pack_head(self.head_r, dev), "head_l": self._pack_head(self.head_l, dev)}
+        if self.backbone_name == "vit_b_16":
+            pack_trunk = lambda name: self._pack_vit_trunk(getattr(self, name), getattr(self, "vit_conv" if name == "backbone" else name + "_vit_conv"), dev)
+        else:
+            pack_trunk = lambda name: self._pack_trunk(getattr(self, name), dev)
         if self.use_glb_feat:
-            P["backbone"] = self._pack_trunk(self.backbone, dev)
+            P["backbone"] = pack_trunk("backbone")
         if not self.no_crops:
             if self.separate_hands:
-                P["hand_backbone_r"] = self._pack_trunk(self.hand_backbone_r, dev)
-                P["hand_backbone_l"] = self._pack_trunk(self.hand_backbone_l, dev)
+                P["hand_backbone_r"] = pack_trunk("hand_backbone_r")
+                P["hand_backbone_l"] = pack_trunk("hand_backbone_l")
             else:
-                P["hand_backbone"] = self._pack_trunk(self.hand_backbone, dev)
+                P["hand_backbone"] = pack_trunk("hand_backbone")
         if self.regress_center_corner:
             for nm, head in (("cc_center", self.center_head), ("cc_corner", self.corner_head)):
                 P[nm] = [pack_linear(cpu(head[0].weight), cpu(head[0].bias), dev), pack_linear(cpu(head[2].weight), cpu(head[2].bias), dev),
@@ -572,7 +646,10 @@ class HandsLight(EngineSwitches, nn.Module):
         """ResNet-50 trunk on B images given as NCHW segments ``[(tensor, first image, n images), ...]`` (the
         reference's input layout, read in place); returns (B,7,7,2048) features (flat tensor).
         (Running stem + layer1 + layer2 per sub-batch of 32-128 images, to keep their HBM-bound 1x1 layers'
-        tensors inside the 256 MB Infinity Cache, was measured 1-18 % SLOWER than whole-job launches.)"""
+        tensors inside the 256 MB Infinity Cache, was measured 1-18 % SLOWER than whole-job launches.)
+        A ViT-B/16 parameter set takes :meth:`_trunk_vit`: same contract."""
+        if "vit" in P:
+            return self._trunk_vit(L, P, segs, B, res_in, stream, tag, cap_B, out, out_off)
         dev = segs[0][0].device
         per = 112 * 112 * 64 * (res_in * res_in) // (224 * 224) + 64      # floats per image of the largest map
         cap = cap_B * per
@@ -604,6 +681,62 @@ class HandsLight(EngineSwitches, nn.Module):
         assert done == B
         feat = out if out is not None else self._buf("feat_" + tag, B * 49 * P["blocks"][-1]["c3"].Cout, dev)
         H, W = self._blocks(L, P["blocks"], b, a, t1, t2, ds, B, Hp, Wp, stream, feat, out_off)
+        return feat, H, W
+
+    def _trunk_vit(self, L, P, segs, B, res_in, stream, tag, cap_B, out=None, out_off=0):
+        """``vit_forward`` (model.py:483-493) on B images given as the segments of :meth:`_trunk`; writes (B,7,7,2048) NHWC
+        features at float offset ``out_off``.  conv_proj as a 16x16 / stride 16 GEMM -> class token + position embedding
+        (hands_vit_tokens_f32) -> 12 x [LayerNorm, qkv GEMM, hands_attention_f32 (197 tokens, 12 heads x 64), out_proj GEMM +
+        residual, LayerNorm, fc1 GEMM + exact GELU, fc2 GEMM + residual] -> encoder.ln on the patch tokens + 2x2 average
+        (hands_vit_tail_f32) -> vit_conv (3x3, BatchNorm folded, ReLU).  Token-major rows are NHWC already: the reference's
+        permute + reshape to (B,768,14,14) never happens.  Workspaces are sized for M = cap_B * 197 rows and kept."""
+        if res_in != VITB_RES:
+            raise ValueError(f"hands_amd.HandsLight: the ViT-B/16 backbone takes {VITB_RES}x{VITB_RES} images, not {res_in}")
+        dev = segs[0][0].device
+        T, Cd, G = VITB_TOKENS, VITB_DIM, VITB_GRID
+        M, capM = B * T, cap_B * T
+        x = self._buf("vit_x_" + tag, capM * Cd, dev); y = self._buf("vit_y_" + tag, capM * Cd, dev)
+        att = self._buf("vit_att_" + tag, capM * Cd, dev)
+        qkv = self._buf("vit_qkv_" + tag, capM * 3 * Cd, dev); hid = self._buf("vit_h_" + tag, capM * VITB_MLP, dev)
+        gemm = lambda pc, src, dst, act=0, **kw: self.engine.conv(L, pc, src, M, 1, 1, dst, act, stream, **kw)
+        lnorm = lambda src, gb, dst: check(L.hands_layernorm_f32(ptr(src), ptr(gb[0]), ptr(gb[1]), ptr(dst), None, 1, M, Cd, VITB_LN_EPS,
+                                                                 stream), "layernorm")
+        # -- conv_proj (`_process_input`): patch rows (B,196,768) into `y`, which the first LayerNorm overwrites afterwards
+        done = 0
+        for src, first, n in segs:
+            if "stem_wide" in P:       # NHWC (.., 224, 224, Cpad) map of the image-level encodings: two launches on its strip view
+                Cp = P["stem_wide"].Cin
+                top, bottom = P["patch_halves"]
+                img = res_in * res_in * Cp
+                step = max(1, (1 << 31) // img - 1)            # the library indexes one launch's input with 31 bits
+                for c0 in range(0, n, step):
+                    nc = min(step, n - c0)
+                    xo, oo = (first + c0) * img, (done + c0) * G * G * Cd
+                    self.engine.conv(L, top, src, nc * G, 16, G, y, False, stream, x_off=xo, out_off=oo, out_hw=(1, G))
+                    self.engine.conv(L, bottom, src, nc * G, 16, G, y, False, stream, x_off=xo + 8 * res_in * Cp, out_off=oo,
+                                     res=y, res_off=oo, out_hw=(1, G))
+                hw = (G, G)
+            else:
+                x4 = self._buf("vit_x4_" + tag, cap_B * res_in * res_in * 4, dev)
+                check(L.hands_nchw3_to_nhwc4_f32(ptr(src, first * 3 * res_in * res_in), ptr(x4), n, res_in, res_in, stream), "nchw->nhwc4")
+                hw = self.engine.conv(L, P["patch"], x4, n, res_in, res_in, y, False, stream, out_off=done * G * G * Cd)
+            assert hw == (G, G)
+            done += n
+        assert done == B
+        check(L.hands_vit_tokens_f32(ptr(y), ptr(P["cls"]), ptr(P["pos"]), ptr(x), B, T, Cd, stream), "vit_tokens")
+        scale = float(VITB_HDIM) ** -0.5
+        for blk in P["blocks"]:
+            lnorm(x, blk["n1"], y)
+            gemm(blk["qkv"], y, qkv)
+            check(L.hands_attention_f32(ptr(qkv), ptr(att), B, T, VITB_HEADS, VITB_HDIM, scale, stream), "attention")
+            gemm(blk["proj"], att, x, res=x)
+            lnorm(x, blk["n2"], y)
+            gemm(blk["fc1"], y, hid, _lib.ACT_GELU)
+            gemm(blk["fc2"], hid, x, res=x)
+        # -- encoder.ln on tokens 1..196 + AvgPool2d(2) -> (B,7,7,768) in `att`; vit_conv -> the caller's feature rows
+        check(L.hands_vit_tail_f32(ptr(x), ptr(P["last"][0]), ptr(P["last"][1]), ptr(att), B, G, Cd, VITB_LN_EPS, stream), "vit_tail")
+        feat = out if out is not None else self._buf("feat_" + tag, B * 49 * P["vit_conv"].Cout, dev)
+        H, W = self.engine.conv(L, P["vit_conv"], att, B, G // 2, G // 2, feat, True, stream, out_off=out_off)
         return feat, H, W
 
     # ---- forward ------------------------------------------------------------------------------

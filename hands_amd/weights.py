@@ -57,6 +57,28 @@ def recipe_tensor(key: str, ref: torch.Tensor) -> torch.Tensor | None:
         return (1.0 + 0.2 * torch.randn(shape, generator=g)).to(ref.dtype)
     if leaf in ("uu", "vv"):
         return None
+    # torchvision ViT-B/16 (hands_light backbone='vit_b_16'): the keys below had no branch (they kept the constructor's random
+    # initialisation); the remaining ViT keys (conv_proj, out_proj, mlp.0 / mlp.3, every bias, encoder.pos_embedding) take the
+    # generic branches further down, unchanged
+    if leaf == "class_token":
+        return (0.5 * torch.randn(shape, generator=g)).to(ref.dtype)
+    if leaf == "in_proj_weight":
+        # rows [q | k | v] on LayerNorm outputs of unit variance: 1 / sqrt(fan_in) gives q, k, v of unit variance, so the
+        # logits (q . k) / sqrt(64) have a standard deviation of ~1 -- O(1-10) as in a trained net (He-scale q, k double it; see
+        # handoccnet's encode_query below for the one-hot failure mode)
+        return (torch.randn(shape, generator=g) * math.sqrt(1.0 / shape[1])).to(ref.dtype)
+    if leaf == "in_proj_bias":
+        return (0.01 * torch.randn(shape, generator=g)).to(ref.dtype)
+    if leaf == "weight" and len(parts) >= 2 and parts[-2] in ("ln_1", "ln_2", "ln"):   # LayerNorm gains (the biases: generic branch)
+        return (1.0 + 0.1 * torch.randn(shape, generator=g)).to(ref.dtype)
+    if len(parts) >= 3 and parts[-3].endswith("vit_conv") and parts[-2] == "2" and leaf != "bias":
+        # the BatchNorm2d of vit_conv (utils.py:31), so that its fold is exercised; its bias keeps the generic branch
+        if leaf == "weight":
+            return (1.0 + 0.1 * torch.randn(shape, generator=g)).to(ref.dtype)
+        if leaf == "running_mean":
+            return (0.1 * torch.randn(shape, generator=g)).to(ref.dtype)
+        if leaf == "running_var":
+            return (1.0 + 0.1 * torch.rand(shape, generator=g)).to(ref.dtype)
     if len(parts) >= 2 and parts[-2] in ("norm", "norm1", "norm2", "last_norm"):   # LayerNorm
         if leaf == "weight":
             return (1.0 + 0.1 * torch.randn(shape, generator=g)).to(ref.dtype)

@@ -422,7 +422,7 @@ int hands_mano_heads_f32(const hands_mano_side* sides, int n_sides, const float*
 int hands_resize_crop_nchw3_to_nhwc4_f32(const float* in, float* out, int B, int Hin, int Win, int S,
                                          int col0, int Wc, hands_stream_t stream);
 
-/* LayerNorm over the last dim C in {256,1024,1280}; out = LN(x)*gamma+beta (+ addvec[row/rows_per_vec]).
+/* LayerNorm over the last dim C in {256,768,1024,1280} (768: the ViT-B/16 trunk of hands_light); out = LN(x)*gamma+beta (+ addvec[row/rows_per_vec]).
  * vit.py:128-151,338 (eps 1e-6), pose_transformer.py:22-33 (eps 1e-5); the optional add is the KPE
  * re-added to the final feature map (hamer_light/model.py:102-104). */
 int hands_layernorm_f32(const float* x, const float* gamma, const float* beta, float* out,
@@ -438,9 +438,28 @@ int hands_kpe_encode_f32(const float* center_angle, const float* corner_angle, f
                          int n_freq, hands_stream_t stream);
 
 /* softmax((scale*q) k^T) v per (batch, head) on fp32 MFMA.  qkv rows are tokens: [q | k | v], each
- * heads*head_dim wide (vit.py:110-126).  Built for T=192, head_dim=80 (ViT-H/16 at 256x192). */
+ * heads*head_dim wide (vit.py:110-126).  Built for T=192, head_dim=80 (ViT-H/16 at 256x192) and for T=197,
+ * head_dim=64 (ViT-B/16 at 224x224: 196 patches + class token, nn.MultiheadAttention's in_proj row order; this shape
+ * used to return HANDS_EINVAL).  T=197 is padded to 208 inside the kernel: padded keys carry zero weight, padded query
+ * rows are not stored -- `out` is written for rows [0, B*197) only.  Any other shape: HANDS_EINVAL. */
 int hands_attention_f32(const float* qkv, float* out, int B, int T, int heads, int head_dim, float scale,
                         hands_stream_t stream);
+
+/* ---- ViT-B/16 trunk of hands_light (HandsLight(backbone='vit_b_16'), hands_light/model.py:483-493; replaces
+ * "only backbone='resnet50' is built").  The encoder's GEMMs and vit_conv run on hands_conv2d_nhwc_f32 /
+ * hands_conv3x3_winograd*_f32, its LayerNorms on hands_layernorm_f32 (C = 768), its attention on hands_attention_f32. ---- */
+
+/* Token assembly (model.py:484-487 + Encoder.forward's `input + pos_embedding`): patch (B, T-1, C) rows of the patch
+ * embedding, class_token (C), pos (T, C) -> x (B, T, C) with x[b,0] = class_token + pos[0], x[b,1+t] = patch[b,t] + pos[1+t].
+ * One add per element (equal to torch.cat + add bit for bit).  C % 4 == 0.  (hands_add_pos_f32 is HaMeR's different rule.) */
+int hands_vit_tokens_f32(const float* patch, const float* class_token, const float* pos, float* x, int B, int T, int C,
+                         hands_stream_t stream);
+
+/* Tail of vit_forward: encoder.ln (eps) on the patch tokens 1..grid*grid of x (B, 1+grid*grid, C), then AvgPool2d(2) of
+ * the grid x grid token map -> out (B, grid/2, grid/2, C) NHWC; each token is normalised first, then four are averaged
+ * (model.py:488-491, utils.py:29).  The class token is never read.  C = 768, grid even. */
+int hands_vit_tail_f32(const float* x, const float* gamma, const float* beta, float* out, int B, int grid, int C, float eps,
+                       hands_stream_t stream);
 
 /* one query token per sample against T context tokens: q (B, heads*64), kv rows [k | v] (B*T,
  * 2*heads*64) -> out (B, heads*64); dots = (q.k)*scale (pose_transformer.py:113-123). */
