@@ -13,7 +13,8 @@ from .frontend import HandsFrontEnd  # noqa: F401
 from .graph import GraphedForward  # noqa: F401
 from .wrapper import HandsWrapper, HaMeRWrapper, HandOccNetWrapper  # noqa: F401
 from .render import MANORenderer, rasterize  # noqa: F401
+from .rend_utils import Renderer, denormalize_images, sideview_transform  # noqa: F401
 
 __all__ = ["HandsLight", "DEFAULT_ARGS", "ManoHeadsPlan", "HAMER", "HAMER_DEFAULT_ARGS", "HandOccNet", "HANDOCC_DEFAULT_ARGS", "xdict", "prefix_dict", "ManoAsset", "synthetic_mano_asset",
            "build_mano_asset", "apply_recipe", "synthetic_inputs", "HandsFrontEnd", "GraphedForward", "HandsWrapper",
-           "HaMeRWrapper", "HandOccNetWrapper", "MANORenderer", "rasterize"]
+           "HaMeRWrapper", "HandOccNetWrapper", "MANORenderer", "rasterize", "Renderer", "denormalize_images", "sideview_transform"]

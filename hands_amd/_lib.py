@@ -53,6 +53,20 @@ class EvalOut(C.Structure):
         "mpjpe_ra_h", "mpjpe_pa_ra_r", "mpjpe_pa_ra_l", "mpjpe_pa_ra_h", "mrrpe_rl", "pix_err_r", "pix_err_l")]
 
 
+class ShadeMesh(C.Structure):
+    """hands_shade_mesh (include/hands_hip.h): one mesh of a shaded picture."""
+    _fields_ = [("workspace", C.c_void_p), ("faces", C.c_void_p), ("valid", C.c_void_p), ("n_verts", C.c_int32),
+                ("n_faces", C.c_int32), ("face_offset", C.c_int32), ("color", C.c_float * 3), ("metallic", C.c_float),
+                ("roughness", C.c_float)]
+
+
+SHADE_MAX_MESHES = 4     # HANDS_SHADE_MAX_MESHES
+
+
+class ShadeScene(C.Structure):
+    _fields_ = [("mesh", ShadeMesh * SHADE_MAX_MESHES), ("n_meshes", C.c_int32)]
+
+
 # name -> argtypes; every function returns int (0 = ok) except the two noted below
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
 class ConvJob(C.Structure):
@@ -128,6 +142,8 @@ SIGNATURES = {
     "hands_frontend_boxes_f32": [_P, _P, _I, _P, _I, _I, _I, C.c_double] + [_P] * 10 + [_P],
     "hands_warp_affine_cubic_norm_f32": [_P, _P, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _P],
     "hands_render_silhouette_f32": [_P, _I, _I, _P, _I, _P, _I, _I, _F, _F, _I, _P, _P, _P, _P],
+    "hands_mesh_prepare_f32": [_P, _I, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P],
+    "hands_render_shaded_f32": [C.POINTER(ShadeScene), _P, _I, _I, _P, _P, _P, _P, _P],
     # host-side packing (csrc/pack.cpp): HOST pointers
     "hands_pack_conv_dims": [_I, _I, _I, _I, _I, C.POINTER(PackedDims)],
     "hands_fold_bn_f32": [_I, C.c_longlong, _P, _P, _P, _P, _P, C.c_double, _P, _P],
@@ -140,7 +156,7 @@ SIGNATURES = {
 }
 EXTRA_SYMBOLS = ("hands_abi_version", "hands_error_string", "hands_conv2d_workspace_floats", "hands_pack_conv3x3_winograd_floats", "hands_conv3x3_winograd_executed_macs",
                  "hands_pack_conv3x3_winograd4_floats", "hands_conv3x3_winograd4_executed_macs",
-                 "hands_conv2d_streamk_workspace_bytes", "hands_stream_is_capturing", "hands_csrc_sha16", "hands_ceiling_mfma_f32")
+                 "hands_conv2d_streamk_workspace_bytes", "hands_stream_is_capturing", "hands_csrc_sha16", "hands_ceiling_mfma_f32", "hands_mesh_workspace_floats")
 
 ABI_VERSION = 5      # HANDS_ABI_VERSION of include/hands_hip.h this wrapper was written against
 _lib = None
@@ -184,6 +200,8 @@ def lib():
     h.hands_csrc_sha16.argtypes = []
     h.hands_ceiling_mfma_f32.restype = C.c_longlong
     h.hands_ceiling_mfma_f32.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p]
+    h.hands_mesh_workspace_floats.restype = C.c_longlong
+    h.hands_mesh_workspace_floats.argtypes = [C.c_int, C.c_int]
     h.hands_error_string.restype = C.c_char_p
     h.hands_error_string.argtypes = [C.c_int]
     _lib = h

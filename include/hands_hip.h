@@ -617,6 +617,53 @@ int hands_warp_affine_cubic_norm_f32(const float* src, const float* trans, float
 int hands_render_silhouette_f32(const float* verts, int ld_verts, int n_verts, const int32_t* faces, int n_faces, const float* K, int B, int S, float sigma, float blur_radius, int faces_per_pixel, float* mask, int32_t* face_idx, float* zbuf, hands_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Shaded renderer of up to four meshes per image (csrc/shade.hip), forward only: the hard z-buffer pictures of
+ * common/rend_utils.py::Renderer (overlay and rotated side views).  The reference draws them with pyrender on OpenGL, which
+ * is third party and absent: "parity unpinned"; the semantics are written out in DESIGN.md section 7 and restated in fp64 in
+ * tests/shade_ref.py.  Two launches per picture:
+ *
+ * hands_mesh_prepare_f32, once per mesh: per (image, vertex) the rigid transform P' = R P + t (T (B, 3, 4) row-major, NULL =
+ *   identity), the area-weighted vertex normal (the sum of (P'1 - P'0) x (P'2 - P'0) over the faces that hold the vertex, in
+ *   ascending face order, gathered through a CSR table: csr_off (n_verts + 1) offsets into csr_face, the face indices; no
+ *   atomics, bit-reproducible; a squared sum <= 1e-30 gives the zero vector; a face whose cross product is not finite adds
+ *   nothing) and the projection of render.hip (K00, K11, K02, K12 only).  Writes 8 floats per vertex into the caller's
+ *   workspace, image b's vertex v at workspace + 8 (b n_verts + v): P'x P'y P'z nx | ny nz xn yn.
+ *   hands_mesh_workspace_floats(B, n_verts) = 8 B n_verts.  A face index of csr_face or a vertex index of faces outside its
+ *   range is skipped.
+ *
+ * hands_render_shaded_f32: one workgroup of 256 lanes per (image, HANDS_SHADE_TILE_W x HANDS_SHADE_TILE_H pixels).  The faces
+ *   of every mesh that is valid for the image (valid (B) floats, NULL or != 0 = present) are binned against the tile in
+ *   (mesh, face) order into a list of HANDS_SHADE_LIST_CAP records in LDS, processed in chunks when it overflows.  A face
+ *   covers a pixel under render.hip's rule (all Z > 0, |area| > 1e-8, w0, w1, w2 > 0 with the area + 1e-8 denominator, both
+ *   windings); depth is perspective-correct (1/z = sum w_i / z_i), the nearest wins, equal depths go to the lower (mesh, face).
+ *   The winner is shaded with interpolated position and normal: glTF 2.0 metallic-roughness, one directional light of
+ *   intensity 3 along the view axis, ambient 0.5, two-sided.  Uncovered pixels take image (B, 3, S, S), or 1.0 when NULL.
+ *   Outputs, each optional (NULL = not written): rgb (B, S, S, 3) floats, rgb8 (B, S, S, 3) = floor(255 clamp(rgb, 0, 1)),
+ *   depth (B, S, S) with 0 where empty, face_id (B, S, S) with -1 where empty, else face index + the mesh's face_offset.
+ *   scene is a HOST pointer, read before the call returns.  No allocation, no synchronisation: capturable.
+ * HANDS_EINVAL (nothing launched): n_meshes outside [1, 4], a NULL workspace / faces, S outside [1, 16384], no output at all. */
+#define HANDS_SHADE_MAX_MESHES 4
+#define HANDS_SHADE_TILE_W 32
+#define HANDS_SHADE_TILE_H 8
+#define HANDS_SHADE_LIST_CAP 384
+typedef struct hands_shade_mesh {
+  const float* workspace;      /* (B, n_verts, 8) written by hands_mesh_prepare_f32 */
+  const int32_t* faces;        /* (n_faces, 3), shared by the batch */
+  const float* valid;          /* (B) or NULL */
+  int32_t n_verts, n_faces;
+  int32_t face_offset;         /* added to the face index in face_id */
+  float color[3];              /* base colour in [0, 1] */
+  float metallic, roughness;
+} hands_shade_mesh;
+typedef struct hands_shade_scene {
+  hands_shade_mesh mesh[HANDS_SHADE_MAX_MESHES];
+  int32_t n_meshes;
+} hands_shade_scene;
+long long hands_mesh_workspace_floats(int B, int n_verts);
+int hands_mesh_prepare_f32(const float* verts, int ld_verts, int n_verts, const int32_t* faces, int n_faces, const int32_t* csr_off, const int32_t* csr_face, const float* K, const float* T, int B, int S, float* workspace, hands_stream_t stream);
+int hands_render_shaded_f32(const hands_shade_scene* scene, const float* image, int B, int S, float* rgb, unsigned char* rgb8, float* depth, int32_t* face_id, hands_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * One-time HOST-side packing (csrc/pack.cpp): reference-layout parameters -> the layouts above.
  * Host pointers only, no GPU call, no allocation kept.  A host in any language packs a reference
  * checkpoint with these and uploads the results; hands_amd/packing.py is a thin ctypes wrapper.
