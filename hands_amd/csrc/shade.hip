@@ -7,9 +7,9 @@
 // Per image: M <= 4 meshes in the camera frame (+x right, +y down, +z forward), each with a base colour and a metallic factor,
 // an optional rigid transform T applied to every vertex first, K (3, 3), image S x S.
 //   pre-pass   P' = R P + t; n_v = normalise(sum over the faces that hold v, ascending, of (P'1 - P'0) x (P'2 - P'0)), the zero
-//              vector when the squared sum is <= 1e-30; projection exactly as render.hip: xn = 2 (K00 X / Z + K02) / S - 1.
-//   coverage   render.hip's rule: all Z > 0, |area| > 1e-8, w0, w1, w2 > 0 with w_i = edge_i / (area + 1e-8); both windings
-//              (no back-face culling: the MANO mesh is open at the wrist).
+//              vector when the squared sum is <= 1e-30; projection: raster_tile.h's, xn = 2 (K00 X / Z + K02) / S - 1.
+//   coverage   raster_tile.h's rule, the silhouette rasteriser's: all Z > 0, |area| > 1e-8, w0, w1, w2 > 0 with
+//              w_i = edge_i / (area + 1e-8); both windings (no back-face culling: the MANO mesh is open at the wrist).
 //   depth      perspective-correct, 1 / z = sum w_i / z_i, b_i = (w_i / z_i) z; the nearest z wins, ties to the lower
 //              (mesh, face): the faces are visited in that order and the comparison is a strict '<'.
 //   shading    P = sum b_i P'_i, n = normalise(sum b_i n_i), v = normalise(-P); n = v if n is zero, n = -n if n.v < 0;
@@ -19,28 +19,25 @@
 //
 // hands_mesh_prepare_f32: one lane per (image, vertex); the normal is GATHERED through a CSR vertex -> face table (no float
 // atomics: bit-reproducible).  8 floats per vertex: P'x P'y P'z nx | ny nz xn yn.
-// hands_render_shaded_f32: shaped like render.hip -- one workgroup of 256 lanes per (image, 32 x 8 pixel tile); 256 faces at a
-// time, one per lane, are tested against the tile and the survivors compacted in (mesh, face) order (ballot + prefix inside a
-// wave, four wave counts through LDS) into a list of 64-byte records; when another 256 might not fit (or at the end) every
-// lane walks the list for its own pixel and keeps the nearest hit only -- z, global face id, two barycentrics -- then the
-// list restarts.  The epilogue fetches the winner's three vertex records from the workspace (L2-resident), shades, composites
-// and stores.  No allocation, no synchronisation: capturable in a hipGraph.
+// hands_render_shaded_f32: the tile geometry, the cull of a face against the tile (its box not grown), the ordered face list in
+// LDS with its barrier protocol and the per-pixel edge functions are raster_tile.h's, shared with render.hip.  This file's
+// own part: the faces of the valid meshes are binned in (mesh, face) order, a record carries 1/z coefficients, and in the
+// walk every lane keeps the nearest hit only -- z, global face id, two barycentrics.  The epilogue fetches the winner's
+// three vertex records from the workspace (L2-resident), shades, composites and stores.  No allocation, no
+// synchronisation: capturable in a hipGraph.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
 #include "hands_hip.h"
 #include "common.h"
+#include "raster_tile.h"
+
+using namespace raster_tile;
 
 namespace {
 
-constexpr int SHADE_THREADS = 256;
-constexpr int TILE_W = HANDS_SHADE_TILE_W, TILE_H = HANDS_SHADE_TILE_H;
-constexpr int LIST_CAP = HANDS_SHADE_LIST_CAP;     // face records per chunk: 24 KB
 constexpr int WS = 8;                              // workspace floats per vertex
-constexpr float K_EPS = 1e-8f;
 constexpr float PI_F = 3.14159265358979323846f;
-static_assert(TILE_W * TILE_H == SHADE_THREADS, "one lane per pixel of the tile");
-static_assert(LIST_CAP >= SHADE_THREADS, "a pass of 256 faces must fit after a flush");
 
 struct Vec3 { float x, y, z; };
 __device__ __forceinline__ Vec3 xform(const float* T, float X, float Y, float Z) {
@@ -64,7 +61,7 @@ __global__ __launch_bounds__(256) void mesh_prepare_kernel(
       const int f = csr_face[j];
       if ((unsigned)f >= (unsigned)n_faces) continue;
       const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
-      if ((unsigned)i0 >= (unsigned)n_verts || (unsigned)i1 >= (unsigned)n_verts || (unsigned)i2 >= (unsigned)n_verts) continue;
+      if (!face_in_range(i0, i1, i2, n_verts)) continue;
       const Vec3 a = xform(T, vb[3 * i0], vb[3 * i0 + 1], vb[3 * i0 + 2]);
       const Vec3 p = xform(T, vb[3 * i1], vb[3 * i1 + 1], vb[3 * i1 + 2]);
       const Vec3 q = xform(T, vb[3 * i2], vb[3 * i2 + 1], vb[3 * i2 + 2]);
@@ -74,11 +71,10 @@ __global__ __launch_bounds__(256) void mesh_prepare_kernel(
     }
     const float s2 = sx * sx + sy * sy + sz * sz;
     const float inv = s2 > 1e-30f ? 1.f / sqrtf(s2) : 0.f;
-    const float* Kb = Kmat + (size_t)b * 9;
-    const float u = Kb[0] * P.x / P.z + Kb[2], w = Kb[4] * P.y / P.z + Kb[5];
+    const float2 ndc = project_ndc(Kmat + (size_t)b * 9, P.x, P.y, P.z, (float)S);
     float4* dst = reinterpret_cast<float4*>(ws + (size_t)i * WS);
     dst[0] = make_float4(P.x, P.y, P.z, inv > 0.f ? sx * inv : 0.f);
-    dst[1] = make_float4(inv > 0.f ? sy * inv : 0.f, inv > 0.f ? sz * inv : 0.f, 2.f * u / (float)S - 1.f, 2.f * w / (float)S - 1.f);
+    dst[1] = make_float4(inv > 0.f ? sy * inv : 0.f, inv > 0.f ? sz * inv : 0.f, ndc.x, ndc.y);
   }
 }
 
@@ -98,21 +94,14 @@ __device__ __forceinline__ float shade_channel(float c, float m, float a2, float
   return clamp01(col);
 }
 
-__global__ __launch_bounds__(SHADE_THREADS) void render_shaded_kernel(
+__global__ __launch_bounds__(THREADS) void render_shaded_kernel(
     const hands_shade_scene sc, const float* __restrict__ image, int S, int tiles_x, int tiles,
     float* __restrict__ rgb, unsigned char* __restrict__ rgb8, float* __restrict__ depth, int32_t* __restrict__ face_id) {
-  __shared__ float4 s_face[LIST_CAP * 4];
-  __shared__ int s_wc[2][SHADE_THREADS / 64];
+  __shared__ FaceList s_list;
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int b = blockIdx.x / tiles, tile = blockIdx.x - b * tiles;
-  const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-  const float fS = (float)S;
-  const int r = ty * TILE_H + (tid >> 5), c = tx * TILE_W + (tid & 31);
-  const float px = (float)(2 * c + 1) / fS - 1.f, py = (float)(2 * r + 1) / fS - 1.f;
-  // sample points of the tile's first and last pixel
-  const float tx0 = (float)(2 * tx * TILE_W + 1) / fS - 1.f, tx1 = (float)(2 * (tx * TILE_W + TILE_W - 1) + 1) / fS - 1.f;
-  const float ty0 = (float)(2 * ty * TILE_H + 1) / fS - 1.f, ty1 = (float)(2 * (ty * TILE_H + TILE_H - 1) + 1) / fS - 1.f;
+  const int tid = threadIdx.x;
+  const TileGeom g = tile_geom(blockIdx.x, tiles, tiles_x, S);
+  const int b = g.b, r = g.r, c = g.c;
 
   float best_z = INFINITY, best_b1 = 0.f, best_b2 = 0.f;
   int best_m = -1, best_f = -1;
@@ -126,77 +115,56 @@ __global__ __launch_bounds__(SHADE_THREADS) void render_shaded_kernel(
     const hands_shade_mesh& M = sc.mesh[m];
     if (M.n_faces <= 0 || (M.valid && M.valid[b] == 0.f)) continue;          // uniform over the workgroup
     const float* wsb = M.workspace + (size_t)b * M.n_verts * WS;
-    for (int base = 0; base < M.n_faces; base += SHADE_THREADS, ++pass) {
+    for (int base = 0; base < M.n_faces; base += THREADS, ++pass) {
       // one face per lane against the tile
       const int f = base + tid;
-      bool keep = false;
-      float x0 = 0, y0 = 0, x1 = 0, y1 = 0, x2 = 0, y2 = 0, z0 = 0, z1 = 0, z2 = 0, area = 0, ylo = 0, yhi = 0;
+      Tri v = {};                                    // zeroed: undefined, this compiler gives the kernel 56 VGPRs, not 48
+      TriCull t;
+      t.keep = false;
       if (f < M.n_faces) {
         const int i0 = M.faces[3 * f], i1 = M.faces[3 * f + 1], i2 = M.faces[3 * f + 2];
-        if ((unsigned)i0 < (unsigned)M.n_verts && (unsigned)i1 < (unsigned)M.n_verts && (unsigned)i2 < (unsigned)M.n_verts) {
+        if (face_in_range(i0, i1, i2, M.n_verts)) {
           const float* a0 = wsb + (size_t)i0 * WS; const float* a1 = wsb + (size_t)i1 * WS; const float* a2 = wsb + (size_t)i2 * WS;
-          x0 = a0[6]; y0 = a0[7]; z0 = a0[2];
-          x1 = a1[6]; y1 = a1[7]; z1 = a1[2];
-          x2 = a2[6]; y2 = a2[7]; z2 = a2[2];
-          area = (x2 - x0) * (y1 - y0) - (y2 - y0) * (x1 - x0);
-          const float xlo = fminf(fminf(x0, x1), x2), xhi = fmaxf(fmaxf(x0, x1), x2);
-          ylo = fminf(fminf(y0, y1), y2);
-          yhi = fmaxf(fmaxf(y0, y1), y2);
-          // every comparison is false for a NaN: such a face is dropped
-          keep = z0 > 0.f && z1 > 0.f && z2 > 0.f && fabsf(area) > K_EPS && xlo <= tx1 && xhi >= tx0 && ylo <= ty1 && yhi >= ty0;
+          v.x0 = a0[6]; v.y0 = a0[7]; v.z0 = a0[2];
+          v.x1 = a1[6]; v.y1 = a1[7]; v.z1 = a1[2];
+          v.x2 = a2[6]; v.y2 = a2[7]; v.z2 = a2[2];
+          t = tri_cull(g, 0.f, v);
         }
       }
-      const unsigned long long bal = __ballot(keep);
-      if (lane == 0) s_wc[pass & 1][wave] = __popcll(bal);
-      __syncthreads();
-      int off = count, total = 0;
-#pragma unroll
-      for (int w = 0; w < SHADE_THREADS / 64; ++w) {
-        const int n = s_wc[pass & 1][w];
-        off += w < wave ? n : 0;
-        total += n;
-      }
-      if (keep) {                                    // count + total <= LIST_CAP: a flush leaves count <= LIST_CAP - 256
-        const int at = off + __popcll(bal & ((1ull << lane) - 1ull));
-        const float inv_area = 1.f / (area + K_EPS);
-        const float iz0 = 1.f / z0, iz1 = 1.f / z1, iz2 = 1.f / z2;
-        float4* dst = s_face + 4 * at;
-        dst[0] = make_float4(x0, y0, x1, y1);
+      bool flush;
+      const int at = list_append(s_list, t.keep, pass, m == last_m && base + THREADS >= M.n_faces, count, flush);
+      if (t.keep) {
+        const float inv_area = 1.f / (t.area + K_EPS);
+        const float iz0 = 1.f / v.z0, iz1 = 1.f / v.z1, iz2 = 1.f / v.z2;
+        float4* dst = s_list.rec + 4 * at;
+        dst[0] = make_float4(v.x0, v.y0, v.x1, v.y1);
         // 1/z = W / z0 + w1 (1/z1 - 1/z0) + w2 (1/z2 - 1/z0) with W = w0 + w1 + w2 = area / (area + eps): the rounding errors of
         // the barycentrics then scale with the face's RANGE of 1/z, not with 1/z itself (render.hip does the same for pz)
-        dst[1] = make_float4(x2, y2, inv_area, area * inv_area * iz0);
+        dst[1] = make_float4(v.x2, v.y2, inv_area, t.area * inv_area * iz0);
         dst[2] = make_float4(iz1 - iz0, iz2 - iz0, iz1, iz2);
-        dst[3] = make_float4(__int_as_float(m), __int_as_float(f), ylo, yhi);
+        dst[3] = make_float4(__int_as_float(m), __int_as_float(f), t.ylo, t.yhi);
       }
-      count += total;
-      const bool last = m == last_m && base + SHADE_THREADS >= M.n_faces;
-      if (count <= LIST_CAP - SHADE_THREADS && !last) continue;            // uniform over the workgroup
+      if (!flush) continue;                          // uniform over the workgroup
 
       // every lane walks the list for its own pixel
       __syncthreads();
       for (int j = 0; j < count; ++j) {
-        const float4 a = s_face[4 * j], bq = s_face[4 * j + 1], cq = s_face[4 * j + 2], dq = s_face[4 * j + 3];
-        if (!(py >= dq.z && py <= dq.w)) continue;
-        const float fx0 = a.x, fy0 = a.y, fx1 = a.z, fy1 = a.w, fx2 = bq.x, fy2 = bq.y;
-        const float q0x = px - fx0, q0y = py - fy0, q1x = px - fx1, q1y = py - fy1, q2x = px - fx2, q2y = py - fy2;
-        const float e0x = fx1 - fx0, e0y = fy1 - fy0, e1x = fx2 - fx1, e1y = fy2 - fy1, e2x = fx0 - fx2, e2y = fy0 - fy2;
-        const float w0 = (q1x * e1y - q1y * e1x) * bq.z;     // edge(p, v1, v2) / (area + eps)
-        const float w1 = (q2x * e2y - q2y * e2x) * bq.z;     // edge(p, v2, v0)
-        const float w2 = (q0x * e0y - q0y * e0x) * bq.z;     // edge(p, v0, v1)
-        if (w0 > 0.f && w1 > 0.f && w2 > 0.f) {
-          const float iz = bq.w + w1 * cq.x + w2 * cq.y;
+        const float4 a = s_list.rec[4 * j], bq = s_list.rec[4 * j + 1], cq = s_list.rec[4 * j + 2], dq = s_list.rec[4 * j + 3];
+        if (!RASTER_TILE_ROW_HITS(g.py, dq.z, dq.w)) continue;
+        const PixelTri p = pixel_tri(g.px, g.py, a.x, a.y, a.z, a.w, bq.x, bq.y, bq.z);
+        if (p.w0 > 0.f && p.w1 > 0.f && p.w2 > 0.f) {
+          const float iz = bq.w + p.w1 * cq.x + p.w2 * cq.y;
           const float z = 1.f / iz;
           if (z < best_z) {                          // strict: a later (higher) face never overtakes an equal depth
             best_z = z;
             best_m = __float_as_int(dq.x);
             best_f = __float_as_int(dq.y);
-            best_b1 = w1 * cq.z * z;
-            best_b2 = w2 * cq.w * z;
+            best_b1 = p.w1 * cq.z * z;
+            best_b2 = p.w2 * cq.w * z;
           }
         }
       }
-      count = 0;                                     // the next pass crosses its barrier (after the wave counts) before any lane
-                                                     // rewrites the list, so every lane has finished this walk by then
+      count = 0;
     }
   }
 
@@ -287,7 +255,7 @@ extern "C" int hands_render_shaded_f32(const hands_shade_scene* scene, const flo
   const int tiles_x = (S + TILE_W - 1) / TILE_W, tiles_y = (S + TILE_H - 1) / TILE_H;
   const long long blocks = (long long)tiles_x * tiles_y * B;
   if (blocks > 0x7fffffffLL) return HANDS_EINVAL;
-  hipLaunchKernelGGL(render_shaded_kernel, dim3((unsigned)blocks), dim3(SHADE_THREADS), 0, (hipStream_t)stream, sc, image, S, tiles_x,
+  hipLaunchKernelGGL(render_shaded_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, (hipStream_t)stream, sc, image, S, tiles_x,
                      tiles_x * tiles_y, rgb, rgb8, depth, face_id);
   HANDS_LAUNCH_CHECK();
 }

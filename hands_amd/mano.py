@@ -160,6 +160,14 @@ def build_mano_asset(is_rhand: bool, allow_synthetic=None) -> ManoAsset:
         "synthetic stand-in with HANDS_SYNTHETIC_MANO=1 (tests / benchmarks only).")
 
 
+def mano_face_lists(mano_assets=None):
+    """``(right, left)`` face lists, (F, 3) int32 and contiguous: ``ManoAsset.faces`` of ``mano_assets=(right, left)``, a side
+    that is None (or all of them) from :func:`build_mano_asset`."""
+    assets = mano_assets if mano_assets is not None else (None, None)
+    assets = [a if a is not None else build_mano_asset(side == 0) for side, a in enumerate(assets)]
+    return tuple(np.ascontiguousarray(np.asarray(a.faces).astype(np.int32)) for a in assets)
+
+
 # buffers smplx.MANO(use_pca=False, flat_hand_mean=False) registers (smplx/body_models.py, SMPL.__init__ +
 # MANO.__init__; third party, absent here -> names restated from the published source, "parity unpinned").
 # Its nn.Parameters (betas, global_orient, hand_pose) and the vertex_joint_selector index buffer are not

@@ -20,7 +20,7 @@ import torch.nn.functional as F_
 
 from . import _lib
 from ._lib import check, ptr
-from .mano import build_mano_asset
+from .mano import mano_face_lists
 
 # include/hands_hip.h: HANDS_SHADE_TILE_W / _H, HANDS_SHADE_LIST_CAP, HANDS_SHADE_MAX_MESHES (tests/test_shaded_render.py
 # holds these against the header)
@@ -145,9 +145,7 @@ class Renderer:
 
     def mano_faces(self):
         if self._mano_faces is None:
-            assets = self._mano_assets if self._mano_assets is not None else (None, None)
-            assets = [a if a is not None else build_mano_asset(side == 0) for side, a in enumerate(assets)]
-            self._mano_faces = tuple(np.ascontiguousarray(np.asarray(a.faces).astype(np.int32)) for a in assets)
+            self._mano_faces = mano_face_lists(self._mano_assets)
         return self._mano_faces
 
     # ---- the call

@@ -20,7 +20,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import check, ptr
-from .mano import build_mano_asset
+from .mano import mano_face_lists
 from .xdict import xdict
 
 # renderer.py:116-123: BlendParams(sigma=1e-5), dist_eps = 1e-6, RasterizationSettings(blur_radius=log(1/dist_eps - 1) * sigma,
@@ -81,9 +81,7 @@ class MANORenderer(nn.Module):
         get = (lambda k, d=None: args.get(k, d)) if isinstance(args, dict) else (lambda k, d=None: getattr(args, k, d))
         self.img_res = int(get("img_res", None) or 224)
         if faces is None:
-            assets = mano_assets if mano_assets is not None else (None, None)
-            assets = [a if a is not None else build_mano_asset(side == 0) for side, a in enumerate(assets)]
-            faces = [a.faces for a in assets]
+            faces = mano_face_lists(mano_assets)
         f_r, f_l = (torch.as_tensor(np.asarray(f.cpu() if torch.is_tensor(f) else f).astype(np.int32)) for f in faces)
         assert f_r.dim() == 2 and f_r.shape[1] == 3 and f_l.dim() == 2 and f_l.shape[1] == 3
         self.mano_faces_r, self.mano_faces_l = f_r.contiguous(), f_l.contiguous()

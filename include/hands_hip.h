@@ -613,7 +613,8 @@ int hands_warp_affine_cubic_norm_f32(const float* src, const float* trans, float
  *   face_idx (B, S, S) int32, -1 where empty, and zbuf (B, S, S), the screen-space interpolated depth, 0 where empty.
  * HANDS_EINVAL (nothing launched): faces_per_pixel outside [1, 10]; a vertex block that does not fit in LDS beside the face
  * list (12 n_verts + 24 608 > 65 536 bytes, i.e. n_verts > 3410); sigma <= 0; blur_radius < 0; S outside [1, 16384].
- * n_faces is unbounded: a tile whose face list overflows its LDS share is processed in chunks. */
+ * n_faces is unbounded: a tile whose face list overflows its LDS share is processed in chunks.  The tile and the list are
+ * the shaded renderer's (HANDS_SHADE_TILE_W, _TILE_H, _LIST_CAP below): the two kernels share csrc/raster_tile.h. */
 int hands_render_silhouette_f32(const float* verts, int ld_verts, int n_verts, const int32_t* faces, int n_faces, const float* K, int B, int S, float sigma, float blur_radius, int faces_per_pixel, float* mask, int32_t* face_idx, float* zbuf, hands_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
@@ -626,22 +627,25 @@ int hands_render_silhouette_f32(const float* verts, int ld_verts, int n_verts, c
  *   identity), the area-weighted vertex normal (the sum of (P'1 - P'0) x (P'2 - P'0) over the faces that hold the vertex, in
  *   ascending face order, gathered through a CSR table: csr_off (n_verts + 1) offsets into csr_face, the face indices; no
  *   atomics, bit-reproducible; a squared sum <= 1e-30 gives the zero vector; a face whose cross product is not finite adds
- *   nothing) and the projection of render.hip (K00, K11, K02, K12 only).  Writes 8 floats per vertex into the caller's
- *   workspace, image b's vertex v at workspace + 8 (b n_verts + v): P'x P'y P'z nx | ny nz xn yn.
+ *   nothing) and the projection of the silhouette renderer (K00, K11, K02, K12 only; csrc/raster_tile.h).  Writes 8 floats
+ *   per vertex into the caller's workspace, image b's vertex v at workspace + 8 (b n_verts + v): P'x P'y P'z nx | ny nz xn yn.
  *   hands_mesh_workspace_floats(B, n_verts) = 8 B n_verts.  A face index of csr_face or a vertex index of faces outside its
  *   range is skipped.
  *
  * hands_render_shaded_f32: one workgroup of 256 lanes per (image, HANDS_SHADE_TILE_W x HANDS_SHADE_TILE_H pixels).  The faces
  *   of every mesh that is valid for the image (valid (B) floats, NULL or != 0 = present) are binned against the tile in
  *   (mesh, face) order into a list of HANDS_SHADE_LIST_CAP records in LDS, processed in chunks when it overflows.  A face
- *   covers a pixel under render.hip's rule (all Z > 0, |area| > 1e-8, w0, w1, w2 > 0 with the area + 1e-8 denominator, both
- *   windings); depth is perspective-correct (1/z = sum w_i / z_i), the nearest wins, equal depths go to the lower (mesh, face).
+ *   covers a pixel under the silhouette renderer's rule (csrc/raster_tile.h holds it for both: all Z > 0, |area| > 1e-8,
+ *   w0, w1, w2 > 0 with the area + 1e-8 denominator, both windings); depth is perspective-correct (1/z = sum w_i / z_i),
+ *   the nearest wins, equal depths go to the lower (mesh, face).
  *   The winner is shaded with interpolated position and normal: glTF 2.0 metallic-roughness, one directional light of
  *   intensity 3 along the view axis, ambient 0.5, two-sided.  Uncovered pixels take image (B, 3, S, S), or 1.0 when NULL.
  *   Outputs, each optional (NULL = not written): rgb (B, S, S, 3) floats, rgb8 (B, S, S, 3) = floor(255 clamp(rgb, 0, 1)),
  *   depth (B, S, S) with 0 where empty, face_id (B, S, S) with -1 where empty, else face index + the mesh's face_offset.
  *   scene is a HOST pointer, read before the call returns.  No allocation, no synchronisation: capturable.
- * HANDS_EINVAL (nothing launched): n_meshes outside [1, 4], a NULL workspace / faces, S outside [1, 16384], no output at all. */
+ * HANDS_EINVAL (nothing launched): n_meshes outside [1, 4], a NULL workspace / faces, S outside [1, 16384], no output at all.
+ * HANDS_SHADE_TILE_W, _TILE_H and _LIST_CAP are the tile and the face list of csrc/raster_tile.h: hands_render_silhouette_f32
+ * uses the same tile and list. */
 #define HANDS_SHADE_MAX_MESHES 4
 #define HANDS_SHADE_TILE_W 32
 #define HANDS_SHADE_TILE_H 8

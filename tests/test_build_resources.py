@@ -12,8 +12,12 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
+RASTER_CEILINGS = {"render.hip": {"render_silhouette_kernel": (86, 24608, 5)},
+                   "shade.hip": {"render_shaded_kernel": (48, 24608, 6), "mesh_prepare_kernel": (54, None, 8)}}
+
+
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-@pytest.mark.parametrize("src", ["conv_igemm.hip", "conv_wino.hip", "mano_lbs.hip", "stem_pool.hip"])
+@pytest.mark.parametrize("src", ["conv_igemm.hip", "conv_wino.hip", "mano_lbs.hip", "stem_pool.hip", "render.hip", "shade.hip"])
 def test_hot_kernels_do_not_spill(tmp_path, src):
     p = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{ROOT}/include", f"-I{ROOT}/hands_amd/csrc",
                         "-fno-fast-math", "-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage", "-c",
@@ -32,6 +36,13 @@ def test_hot_kernels_do_not_spill(tmp_path, src):
             vg, ag = int(re.search(r"VGPRs: (\d+)", b).group(1)), int(re.search(r"AGPRs: (\d+)", b).group(1))
             lds = int(re.search(r"LDS Size \[bytes/block\]: (\d+)", b).group(1))
             assert vg + ag <= 168 and 40960 < lds <= 54272, (b.split()[0], vg, ag, lds)
+    # the two mesh rasterisers and the pre-pass: no more registers or LDS, no lower occupancy, than before they shared
+    # csrc/raster_tile.h (VGPRs, static LDS bytes per workgroup or None, waves per SIMD)
+    for kernel, (vg_max, lds_max, occ_min) in RASTER_CEILINGS.get(src, {}).items():
+        b = next(b for b in re.split(r"Function Name: ", p.stderr)[1:] if kernel in b.split()[0])
+        vg, lds = int(re.search(r"VGPRs: (\d+)", b).group(1)), int(re.search(r"LDS Size \[bytes/block\]: (\d+)", b).group(1))
+        occ = int(re.search(r"Occupancy \[waves/SIMD\]: (\d+)", b).group(1))
+        assert vg <= vg_max and (lds_max is None or lds <= lds_max) and occ >= occ_min, (kernel, vg, lds, occ)
     names = re.findall(r"Function Name: (\S+)", p.stderr)
     scratch = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", p.stderr)]
     spills = [int(v) for v in re.findall(r"VGPRs Spill: (\d+)", p.stderr)]
