@@ -12,5 +12,68 @@ static inline int hands_grid_1d(long long work, int block, int cap = 256 * 8) {
   return (int)g;
 }
 
-// vit_b.hip: the (T, head_dim) = (197, 64) launch behind hands_attention_f32 (transformer.hip)
-__attribute__((visibility("hidden"))) int hands_detail_attention_t197_d64(const float* qkv, float* out, int B, int heads, float scale, hipStream_t stream);
+// ---- device side ---------------------------------------------------------------------------------------------------------
+typedef float f32x4 __attribute__((ext_vector_type(4)));      // MFMA 16x16 accumulator
+typedef float f32x16 __attribute__((ext_vector_type(16)));    // MFMA 32x32 accumulator
+
+__device__ __forceinline__ float f4e(const float4& v, int t) {
+  return t == 0 ? v.x : (t == 1 ? v.y : (t == 2 ? v.z : v.w));
+}
+
+// exp(x) for finite x <= 0: exp2 of a compensated x * log2(e) (v_exp_f32 on [-0.5, 0.5] + v_ldexp_f32, ~1 ulp; the
+// library's expf carries range checks that cannot trigger here)
+__device__ __forceinline__ float exp_nonpos(float x) {
+  const float L2E_HI = 1.44269502162933349609375f, L2E_LO = 1.925963033500011e-08f;
+  const float n = rintf(x * L2E_HI);
+  float f = fmaf(x, L2E_HI, -n);                           // x * log2(e) - n with one rounding
+  f = fmaf(x, L2E_LO, f);
+  return ldexpf(__builtin_amdgcn_exp2f(f), (int)n);
+}
+
+// 16 bytes at p when `real`, zeros otherwise (padded tokens: nothing is read past the tensor)
+__device__ __forceinline__ float4 ld4_or_zero(bool real, const float* p) {
+  float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (real) r = *reinterpret_cast<const float4*>(p);
+  return r;
+}
+
+// LayerNorm of one row of C = 256 * VPL floats by one wave: lane holds the float4 slots lane + 64 i.  Two passes over the
+// row in registers (mean, then the variance of the centred values), each closed by a __shfl_xor tree, then the affine
+// y = (x - mean) * rstd * gamma + beta, handed slot by slot to emit(i, y) -- the caller's store.
+template <int VPL, class Emit>
+__device__ __forceinline__ void layernorm_row(const float* x_row, const float* gamma, const float* beta, float eps, int lane,
+                                              Emit emit) {
+  constexpr int C = 256 * VPL;
+  const float4* xr = reinterpret_cast<const float4*>(x_row);
+  float4 v[VPL];
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) {
+    v[i] = xr[lane + 64 * i];
+    s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  const float mean = s / (float)C;
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) {
+    const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
+    q += (a * a + b * b) + (c * c + d * d);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
+  const float rstd = 1.0f / sqrtf(q / (float)C + eps);
+  const float4* g4 = reinterpret_cast<const float4*>(gamma);
+  const float4* b4 = reinterpret_cast<const float4*>(beta);
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) {
+    const float4 g = g4[lane + 64 * i], bb = b4[lane + 64 * i];
+    float4 y;
+    y.x = (v[i].x - mean) * rstd * g.x + bb.x;
+    y.y = (v[i].y - mean) * rstd * g.y + bb.y;
+    y.z = (v[i].z - mean) * rstd * g.z + bb.z;
+    y.w = (v[i].w - mean) * rstd * g.w + bb.w;
+    emit(i, y);
+  }
+}

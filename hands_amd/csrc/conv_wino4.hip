@@ -53,7 +53,6 @@ extern "C" int hands_debug_w4prof(void* dst, int clear) {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_void_t;
 

@@ -11,11 +11,6 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ float f4e(const float4& v, int t) {
-  return t == 0 ? v.x : (t == 1 ? v.y : (t == 2 ? v.z : v.w));
-}
 __device__ __forceinline__ float4 f4add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
 
@@ -242,14 +237,6 @@ __global__ void __launch_bounds__(256) spatial_softmax_kernel(const float* __res
 // sum hoisted out of the N x N product), optional residual (SET: query + attn).
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) const void gbl_void_t;
-
-__device__ __forceinline__ float exp_nonpos(float x) {     // x <= 0, finite
-  const float L2E_HI = 1.44269502162933349609375f, L2E_LO = 1.925963033500011e-08f;
-  const float n = rintf(x * L2E_HI);
-  float f = fmaf(x, L2E_HI, -n);                           // x * log2(e) - n with one rounding
-  f = fmaf(x, L2E_LO, f);
-  return ldexpf(__builtin_amdgcn_exp2f(f), (int)n);
-}
 
 template <bool FOLD>
 __global__ void __launch_bounds__(256, 2) flash_attention64_kernel(const float* __restrict__ q, const float* __restrict__ k,

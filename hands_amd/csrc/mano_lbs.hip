@@ -241,8 +241,6 @@ static_assert(BLEND_K == 146 && BLEND_KPAD == 160 && BLEND_KPAD - BLEND_K >= 14 
               "k = 145 must be the last non-zero column, in the last of ten 16-wide steps");
 static_assert(CHUNK_M == 3 * CHUNK_V && CHUNK_M == 12 * 16, "a chunk is 12 row tiles of 16 outputs");
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 template <bool AA_INPUT>
 __global__ void __launch_bounds__(256, 2) mano_heads_kernel(ManoHeadsArgs a) {
   // phase-1 scratch (joint rotations, rest joints, global transforms) is dead once A is built: it shares its

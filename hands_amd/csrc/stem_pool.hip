@@ -25,8 +25,6 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int PT_H = 7, PT_W = 8;                 // pooled tile
 constexpr int CT_H = 2 * PT_H + 1, CT_W = 2 * PT_W + 1;   // 15 x 17 convolution pixels (255 <= 256)
 constexpr int IP_H = 2 * CT_H + 5, IP_W = 2 * CT_W + 5;   // 35 x 39 input pixels
@@ -34,8 +32,6 @@ constexpr int IP_EVEN = (IP_W + 1) / 2;           // 20 even columns, then 19 od
 constexpr int IP_ROW = 40;                        // 16-byte slots per patch row
 constexpr int KPAD = 208;                         // 49 taps x 4 channels, padded to 13 steps of 16
 constexpr int ST_ROW = 20;                        // staging row: 16 channels + 4 pad floats (5 slots: odd)
-
-__device__ __forceinline__ float f4e(const float4& v, int t) { return t == 0 ? v.x : (t == 1 ? v.y : (t == 2 ? v.z : v.w)); }
 
 __device__ __forceinline__ float act_scalar(float v, int act) {
   if (act == HANDS_ACT_RELU) return fmaxf(v, 0.f);

@@ -11,23 +11,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// exp(x) for finite x <= 0: exp2 of a compensated x * log2(e) (v_exp_f32 on [-0.5, 0.5] + v_ldexp_f32, ~1 ulp; the
-// library's expf carries range checks that cannot trigger here)
-__device__ __forceinline__ float exp_nonpos(float x) {
-  const float L2E_HI = 1.44269502162933349609375f, L2E_LO = 1.925963033500011e-08f;
-  const float n = rintf(x * L2E_HI);
-  float f = fmaf(x, L2E_HI, -n);
-  f = fmaf(x, L2E_LO, f);
-  return ldexpf(__builtin_amdgcn_exp2f(f), (int)n);
-}
-
-__device__ __forceinline__ float f4e(const float4& v, int t) {
-  return t == 0 ? v.x : (t == 1 ? v.y : (t == 2 ? v.z : v.w));
-}
-
 // ---- F.interpolate(bilinear, align_corners=False) + column crop, NCHW3 -> NHWC4 ---------------------
 // model.py:82-100: resize (Hin,Win) -> (S,S), then keep columns [col0, col0+Wc).
 __global__ void resize_crop_kernel(const float* __restrict__ in, float4* __restrict__ out, int B, int Hin,
@@ -68,41 +51,12 @@ __global__ void __launch_bounds__(256) layernorm_kernel(const float* __restrict_
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
-  const float4* xr = reinterpret_cast<const float4*>(x + (long long)row * C);
-  float4 v[VPL];
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    v[i] = xr[lane + 64 * i];
-    s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  const float mean = s / (float)C;
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
-    q += (a * a + b * b) + (c * c + d * d);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
-  const float rstd = 1.0f / sqrtf(q / (float)C + eps);
-  const float4* g4 = reinterpret_cast<const float4*>(gamma);
-  const float4* b4 = reinterpret_cast<const float4*>(beta);
   const float4* a4 = addvec ? reinterpret_cast<const float4*>(addvec + (long long)(row / rows_per_vec) * C) : nullptr;
   float4* orow = reinterpret_cast<float4*>(out + (long long)row * C);
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) {
-    const float4 g = g4[lane + 64 * i], bb = b4[lane + 64 * i];
-    float4 y;
-    y.x = (v[i].x - mean) * rstd * g.x + bb.x;
-    y.y = (v[i].y - mean) * rstd * g.y + bb.y;
-    y.z = (v[i].z - mean) * rstd * g.z + bb.z;
-    y.w = (v[i].w - mean) * rstd * g.w + bb.w;
+  layernorm_row<VPL>(x + (long long)row * C, gamma, beta, eps, lane, [&](int i, float4 y) {
     if (a4) { const float4 a = a4[lane + 64 * i]; y.x += a.x; y.y += a.y; y.z += a.z; y.w += a.w; }
     orow[lane + 64 * i] = y;
-  }
+  });
 }
 
 // ---- x[b,t,:] = ((x + pos[1+t]) + pos[0]) + vec[b]   (vit.py:326-330) --------------------------------
@@ -144,7 +98,9 @@ __global__ void kpe_encode_kernel(const float* __restrict__ center, const float*
 }
 
 // ---- multi-head self-attention on fp32 MFMA -----------------------------------------------------------
-// One workgroup per (head, crop): T = 16 * TW tokens, TW waves of 16 queries each, on v_mfma_f32_16x16x4_f32.
+// One workgroup per (head, crop): TR real tokens in T = 16 * TW token slots, TW waves of 16 queries each, on
+// v_mfma_f32_16x16x4_f32.  Two instantiations: <12, 80, 192> (ViT-H/16 of hamer_light, TR == T) and <13, 64, 197> (ViT-B/16 of
+// hands_light at 224x224: 196 patches + class token, padded to 208 = 13 blocks of 16).
 //   S^T[key][query] = sum_d K[key][d] * (scale * Q[query][d])      (K rows = MFMA A, Q rows = MFMA B)
 // A lane holds, for ITS query (lane & 15), four keys of every 16-key block (keys 16 kb + 4 g + i, g = lane >> 4): the
 // softmax over keys is lane-local plus two exchanges (lane ^ 16, lane ^ 32).  The probabilities feed the second product
@@ -152,6 +108,7 @@ __global__ void kpe_encode_kernel(const float* __restrict__ center, const float*
 //   O^T[d][query] = sum_key V^T[d][key] * P[key][query]           (V^T rows = MFMA A, P = MFMA B)
 // where MFMA step i of key block kb contracts the keys {16 kb + 4 g + i : g = 0..3} -- exactly the keys the four lane
 // groups hold in accumulator register i.
+// Fixed summation order per (head, crop): results do not depend on the batch size.
 //
 // Why 12 waves of 16 queries and not 6 waves of 32 (the form of rounds 1-3, on v_mfma_f32_32x32x2_f32): tools/prof_attn.py
 // (per-wave phase stamps + HW_ID) showed that a 6-wave workgroup lands 2-2-1-1 on a CU's four SIMDs -- with two such
@@ -162,14 +119,46 @@ __global__ void kpe_encode_kernel(const float* __restrict__ center, const float*
 // SIMD, so one workgroup's fill and barrier phases run under the other's MFMAs; V is requested right after the first barrier
 // and waits in registers under Q.K^T.  358 -> 266 us per call at 128 crops (round 4; own LDS regions for K and V^T, one
 // workgroup per CU: 284 us).
+//
+// A token count that is NOT a multiple of 16 (PAD: TR < T; only the last 16-token block has padded tokens).  Every PAD-only
+// operation below is behind `!PAD ||` and folds away when TR == T:
+//   * Padded K rows (tokens TR..T-1) and padded V^T columns are written as ZEROS, so every LDS word an MFMA reads is defined:
+//     the scores of padded keys are exactly 0 (finite), and their probabilities are set to exactly 0 before the second
+//     product, so 0 * 0 is all they ever contribute.
+//   * Padded keys do not reach the softmax: they are left out of the row maximum and of the sum.
+//   * Padded query rows (the last wave's queries TR..T-1) load zeros instead of reading past the tensor, run through the same
+//     instruction stream (uniform softmax over finite scores, no NaN), and are never stored: nothing beyond row TR-1 of a
+//     crop's output is written.
+// Partition for 197 tokens: ONE WAVE PER 16-QUERY BLOCK, 13 waves = 832 threads per (head, crop).  Thirteen blocks do not
+// divide over four SIMDs whatever is done with them.  The alternatives were (a) twelve waves that share the 13th block -- its
+// 5 real queries would need a cross-wave softmax (keys split over waves: an LDS round trip and two more barriers for 2.5 % of
+// the queries) -- or (b) seven waves of two blocks (the 6-wave imbalance measured above, plus a half-empty 14th block = 7 %
+// wasted MFMAs against 5.6 % here).  With 13 waves a workgroup sits 4-3-3-3 on the SIMDs.  55.3 KB of LDS (208 x 68 floats of
+// K, then 64 x 212 of V^T in its place) would let two workgroups share a CU, but the registers do not: 52 score registers +
+// 16 of Q + 16 of parked V + the K fragment are 119 VGPRs, four waves per SIMD, so ONE workgroup is resident per CU and its
+// fill and barrier phases are not hidden under another's MFMAs as they are for ViT-H (two resident workgroups would need 7
+// waves on a SIMD = 72 VGPRs: the compiler reaches that only by spilling 164 bytes per lane).  That, and the tail block
+// (11/16 of one wave's MFMAs = 5.3 % of the launch), is why <13, 64, 197>'s rate per algorithmic FLOP is below
+// <12, 80, 192>'s; docs/EXPERIMENTS.md has both, measured in one run.
 template <int TW, int D>
 constexpr int attention_lds_bytes() {
   return 4 * (16 * TW * (D + 4) > D * (16 * TW + 4) ? 16 * TW * (D + 4) : D * (16 * TW + 4));     // K, then V^T in its place
 }
 
-template <int TW, int D>
-__global__ void __launch_bounds__(64 * TW) __attribute__((amdgpu_waves_per_eu(6, 6))) attention_kernel(const float* __restrict__ qkv, float* __restrict__ out, int heads, float scale) {
-  constexpr int T = 16 * TW;
+// The register allocator's target, waves per SIMD: a workgroup's waves on its fullest SIMD, times the workgroups per CU the
+// reasoning above arrives at -- two when the waves divide evenly over the four SIMDs (3 x 2 = 6: 80 registers), one
+// otherwise (13 waves: 4, up to 128 registers).
+template <int TW>
+constexpr int attention_waves_per_simd() {
+  return TW % 4 == 0 ? 2 * (TW / 4) : (TW + 3) / 4;
+}
+
+template <int TW, int D, int TR>
+__global__ void __launch_bounds__(64 * TW)
+__attribute__((amdgpu_waves_per_eu(attention_waves_per_simd<TW>(), attention_waves_per_simd<TW>())))
+attention_kernel(const float* __restrict__ qkv, float* __restrict__ out, int heads, float scale) {
+  constexpr int T = 16 * TW;         // token slots
+  constexpr bool PAD = TR != T;
   constexpr int KR = D + 4;          // K row (floats): (D + 4) * 4 B = an odd number of 16-byte slots for D = 80
   constexpr int VR = T + 4;          // V^T row
   constexpr int NT = 64 * TW;
@@ -177,6 +166,7 @@ __global__ void __launch_bounds__(64 * TW) __attribute__((amdgpu_waves_per_eu(6,
   constexpr int DB = D / 16;         // 16-row blocks of V^T / O^T
   constexpr int FILL = T * (D / 4) / NT;
   static_assert(D % 16 == 0 && T * (D / 4) % NT == 0 && NT % T == 0, "fill loops assume whole iterations");
+  static_assert(TR <= T && TR > T - 16, "TR real tokens fill all but the last 16-token block");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* sK = lds;                   // [T][KR]
   float* sV = lds;                   // [D][VR]  (V transposed) in K's place, once every wave is done with K
@@ -185,17 +175,17 @@ __global__ void __launch_bounds__(64 * TW) __attribute__((amdgpu_waves_per_eu(6,
   const int C = heads * D;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l15 = lane & 15, g = lane >> 4;
-  const float* base = qkv + (long long)b * T * 3 * C + h * D;
+  const float* base = qkv + (long long)b * TR * 3 * C + h * D;
 
-  // K tile -> LDS: consecutive lanes walk the 16-byte slots of a token's row (coalesced 320-byte rows); all loads of a
-  // thread in flight before its first LDS store
+  // K tile -> LDS (rows TR..T-1 zero): consecutive lanes walk the 16-byte slots of a token's row (coalesced 320-byte rows
+  // for D = 80); all loads of a thread in flight before its first LDS store
   {
     float4 kv[FILL];
 #pragma unroll
     for (int it = 0; it < FILL; ++it) {
       const int i = tid + it * NT;
       const int t = i / (D / 4), dq = i - t * (D / 4);
-      kv[it] = *reinterpret_cast<const float4*>(base + (long long)t * 3 * C + C + dq * 4);
+      kv[it] = ld4_or_zero(!PAD || t < TR, base + (long long)t * 3 * C + C + dq * 4);
     }
 #pragma unroll
     for (int it = 0; it < FILL; ++it) {
@@ -206,12 +196,14 @@ __global__ void __launch_bounds__(64 * TW) __attribute__((amdgpu_waves_per_eu(6,
   }
   // this wave's Q fragments, pre-scaled (vit.py:118 scales q before the matmul): lane (query l15, group g) holds
   // d = 16 kk + 4 g + j
+  const int query = wave * 16 + l15;
+  const bool qreal = !PAD || query < TR;
   float4 qf[NKK];
   {
-    const float* qrow = base + (long long)(wave * 16 + l15) * 3 * C + 4 * g;
+    const float* qrow = base + (long long)(qreal ? query : 0) * 3 * C + 4 * g;
 #pragma unroll
     for (int kk = 0; kk < NKK; ++kk) {
-      float4 v = *reinterpret_cast<const float4*>(qrow + kk * 16);
+      float4 v = ld4_or_zero(qreal, qrow + kk * 16);
       v.x *= scale; v.y *= scale; v.z *= scale; v.w *= scale;
       qf[kk] = v;
     }
@@ -223,7 +215,8 @@ __global__ void __launch_bounds__(64 * TW) __attribute__((amdgpu_waves_per_eu(6,
   const int ft = tid % T, fq = tid / T;
   float4 vv[FILL];
 #pragma unroll
-  for (int it = 0; it < FILL; ++it) vv[it] = *reinterpret_cast<const float4*>(base + (long long)ft * 3 * C + 2 * C + (fq + it * (NT / T)) * 4);
+  for (int it = 0; it < FILL; ++it)
+    vv[it] = ld4_or_zero(!PAD || ft < TR, base + (long long)ft * 3 * C + 2 * C + (fq + it * (NT / T)) * 4);
 
   // S^T = K . (scale Q)^T: TW independent accumulation chains (one per key block), the k-step outermost
   f32x4 s[TW];
@@ -243,7 +236,8 @@ __global__ void __launch_bounds__(64 * TW) __attribute__((amdgpu_waves_per_eu(6,
     }
   }
   __syncthreads();   // every wave is done with K
-  // V^T -> LDS in K's place (lanes walk tokens: the transposed scalar writes are conflict-free)
+  // V^T -> LDS in K's place (lanes walk tokens: the transposed scalar writes are conflict-free; columns TR..T-1 zero,
+  // columns T..VR-1 are never read)
 #pragma unroll
   for (int it = 0; it < FILL; ++it) {
     float* d = sV + (fq + it * (NT / T)) * 4 * VR + ft;
@@ -253,19 +247,27 @@ __global__ void __launch_bounds__(64 * TW) __attribute__((amdgpu_waves_per_eu(6,
     d[3 * VR] = vv[it].w;
   }
   // softmax over the keys of this lane's query: exp(x - max) * (1 / sum): one reciprocal per query; e * (1 / sum) vs
-  // e / sum differ by the last rounding only
-  float m = s[0][0];
+  // e / sum differ by the last rounding only.  Register r of key block kb holds key 16 kb + 4 g + r: only registers
+  // r >= nreal of the last block hold padded keys
+  constexpr int LB = TW - 1;
+  const int nreal = TR - 16 * LB - 4 * g;
+  float m = s[0][0];                 // key 0 (g = 0) .. key 12 (g = 3): always real
 #pragma unroll
   for (int kb = 0; kb < TW; ++kb)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) m = fmaxf(m, s[kb][r]);
+    for (int r = 0; r < 4; ++r) m = (!PAD || kb < LB || r < nreal) ? fmaxf(m, s[kb][r]) : m;
   m = fmaxf(m, __shfl_xor(m, 16));
   m = fmaxf(m, __shfl_xor(m, 32));
   float sum = 0.f;
 #pragma unroll
   for (int kb = 0; kb < TW; ++kb)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) { s[kb][r] = exp_nonpos(s[kb][r] - m); sum += s[kb][r]; }
+    for (int r = 0; r < 4; ++r) {
+      const bool real = !PAD || kb < LB || r < nreal;
+      const float e = exp_nonpos(real ? s[kb][r] - m : 0.f);
+      s[kb][r] = real ? e : 0.f;
+      sum += s[kb][r];
+    }
   sum += __shfl_xor(sum, 16);
   sum += __shfl_xor(sum, 32);
   const float inv_sum = 1.0f / sum;
@@ -292,11 +294,14 @@ __global__ void __launch_bounds__(64 * TW) __attribute__((amdgpu_waves_per_eu(6,
       }
     }
   }
-  // O^T[d = 16 db + 4 g + i][query l15] -> out[(b*T + query)*C + h*D + d], 4 consecutive d per store
-  float* orow = out + ((long long)b * T + wave * 16 + l15) * C + h * D + 4 * g;
+  // O^T[d = 16 db + 4 g + i][query l15] -> out[(b*TR + query)*C + h*D + d], 4 consecutive d per store; padded queries
+  // store nothing
+  if (qreal) {
+    float* orow = out + ((long long)b * TR + query) * C + h * D + 4 * g;
 #pragma unroll
-  for (int db = 0; db < DB; ++db)
-    *reinterpret_cast<float4*>(orow + db * 16) = make_float4(o[db][0], o[db][1], o[db][2], o[db][3]);
+    for (int db = 0; db < DB; ++db)
+      *reinterpret_cast<float4*>(orow + db * 16) = make_float4(o[db][0], o[db][1], o[db][2], o[db][3]);
+  }
 }
 
 // ---- single-query cross-attention (decoder head): one wave per (batch, head), head dim 64 ------------
@@ -358,6 +363,27 @@ __global__ void rot6d_cols_kernel(const float* __restrict__ pose6d, int ld6, flo
   }
 }
 
+// hands_attention_f32's launch of one instantiation.  More than the 64 KB default cap of dynamic LDS (<12, 80, 192>: 64.5 KB)
+// needs the kernel's limit raised, once per device; an instantiation under the cap (<13, 64, 197>: 56 576 B) makes no runtime
+// call before its launch -- it runs inside stream capture.
+template <int TW, int D, int TR>
+int launch_attention(const float* qkv, float* out, int B, int heads, float scale, hipStream_t stream) {
+  constexpr int LDS = attention_lds_bytes<TW, D>();
+  if constexpr (LDS > 64 * 1024) {
+    static std::atomic<int> lds_set[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return HANDS_EINVAL;
+    if (!lds_set[dev].load(std::memory_order_acquire)) {
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_kernel<TW, D, TR>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+      if (e != hipSuccess) return (int)e;
+      lds_set[dev].store(1, std::memory_order_release);
+    }
+  }
+  hipLaunchKernelGGL((attention_kernel<TW, D, TR>), dim3(heads, B), dim3(64 * TW), LDS, stream, qkv, out, heads, scale);
+  HANDS_LAUNCH_CHECK();
+}
+
 }  // namespace
 
 extern "C" {
@@ -410,26 +436,11 @@ int hands_kpe_encode_f32(const float* center_angle, const float* corner_angle, f
 int hands_attention_f32(const float* qkv, float* out, int B, int T, int heads, int head_dim, float scale,
                         hands_stream_t stream) {
   if (!qkv || !out || B <= 0 || heads <= 0) return HANDS_EINVAL;
-  if (T == 192 && head_dim == 80) {
-    // 127 KB of dynamic LDS (> the 64 KB default cap of a launch): raise the kernel's limit once per device
-    static std::atomic<int> lds_set[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return HANDS_EINVAL;
-    if (!lds_set[dev].load(std::memory_order_acquire)) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_kernel<12, 80>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, attention_lds_bytes<12, 80>());
-      if (e != hipSuccess) return (int)e;
-      lds_set[dev].store(1, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((attention_kernel<12, 80>), dim3(heads, B), dim3(768), (attention_lds_bytes<12, 80>()), (hipStream_t)stream,
-                       qkv, out, heads, scale);
-  } else if (T == 197 && head_dim == 64) {
-    // ViT-B/16 at 224x224 (196 patches + class token): attention_pad_kernel<13, 64, 197> of vit_b.hip
-    return hands_detail_attention_t197_d64(qkv, out, B, heads, scale, (hipStream_t)stream);
-  } else {
-    return HANDS_EINVAL;
-  }
-  HANDS_LAUNCH_CHECK();
+  if (T == 192 && head_dim == 80)      // ViT-H/16 at 256x192
+    return launch_attention<12, 80, 192>(qkv, out, B, heads, scale, (hipStream_t)stream);
+  if (T == 197 && head_dim == 64)      // ViT-B/16 at 224x224 (196 patches + class token)
+    return launch_attention<13, 64, 197>(qkv, out, B, heads, scale, (hipStream_t)stream);
+  return HANDS_EINVAL;
 }
 
 int hands_cross_attention_1q_f32(const float* q, const float* kv, float* out, int B, int T, int heads,

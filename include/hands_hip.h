@@ -440,8 +440,9 @@ int hands_kpe_encode_f32(const float* center_angle, const float* corner_angle, f
 /* softmax((scale*q) k^T) v per (batch, head) on fp32 MFMA.  qkv rows are tokens: [q | k | v], each
  * heads*head_dim wide (vit.py:110-126).  Built for T=192, head_dim=80 (ViT-H/16 at 256x192) and for T=197,
  * head_dim=64 (ViT-B/16 at 224x224: 196 patches + class token, nn.MultiheadAttention's in_proj row order; this shape
- * used to return HANDS_EINVAL).  T=197 is padded to 208 inside the kernel: padded keys carry zero weight, padded query
- * rows are not stored -- `out` is written for rows [0, B*197) only.  Any other shape: HANDS_EINVAL. */
+ * used to return HANDS_EINVAL): attention_kernel<12,80,192> and attention_kernel<13,64,197> of csrc/transformer.hip, one
+ * kernel template.  T=197 is padded to 208 inside the kernel: padded keys carry zero weight, padded query rows are not
+ * stored -- `out` is written for rows [0, B*197) only.  Any other shape: HANDS_EINVAL. */
 int hands_attention_f32(const float* qkv, float* out, int B, int T, int heads, int head_dim, float scale,
                         hands_stream_t stream);
 

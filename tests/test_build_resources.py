@@ -85,23 +85,34 @@ def test_fp32_conv_kernels_keep_four_workgroups_per_cu(tmp_path):
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 def test_vit_attention_fits_two_workgroups_per_cu(tmp_path):
-    """attention_kernel<12, 80> (csrc/transformer.hip): 12 waves per workgroup (a multiple of the 4 SIMDs: three each), <= 80
+    """attention_kernel<12, 80, 192> (csrc/transformer.hip): 12 waves per workgroup (a multiple of the 4 SIMDs: three each), <= 80
     registers (six waves per SIMD) and <= 80 KB of dynamic LDS, i.e. TWO workgroups per CU, no scratch beyond a handful of
     spilled registers.  The 6-wave / 168-register form of rounds 1-3 fitted one workgroup per CU with a 2-2-1-1 SIMD load
-    (tools/prof_attn.py) and ran 35 % slower."""
+    (tools/prof_attn.py) and ran 35 % slower.
+    attention_kernel<13, 64, 197>, the padded instantiation of the same body: 13 waves put four on one SIMD, so 512 / 4 = 128
+    registers is the residency limit of its one workgroup per CU; nothing spilled; and its dynamic LDS stays under the 64 KB
+    a launch may ask for without a hipFuncSetAttribute call (it is launched inside stream capture)."""
     src = os.path.join(ROOT, "hands_amd", "csrc", "transformer.hip")
     p = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{ROOT}/include", f"-I{ROOT}/hands_amd/csrc",
                         "-fno-fast-math", "-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o",
                         str(tmp_path / "o.o")], capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
-    b = next(b for b in re.split(r"Function Name: ", p.stderr)[1:] if "attention_kernelILi12ELi80" in b.split()[0])
-    vg = int(re.search(r"VGPRs: (\d+)", b).group(1))
-    spill = int(re.search(r"VGPRs Spill: (\d+)", b).group(1))
-    occ = int(re.search(r"Occupancy \[waves/SIMD\]: (\d+)", b).group(1))
+    blocks = re.split(r"Function Name: ", p.stderr)[1:]
+    field = lambda b, pat: int(re.search(pat, b).group(1))
+    b = next(b for b in blocks if "attention_kernelILi12ELi80ELi192E" in b.split()[0])
+    vg, spill, occ = field(b, r" VGPRs: (\d+)"), field(b, r"VGPRs Spill: (\d+)"), field(b, r"Occupancy \[waves/SIMD\]: (\d+)")
     assert vg <= 80 and occ >= 6 and spill <= 16, (vg, occ, spill)
     text = open(src).read()
-    assert "dim3(768)" in text and "attention_kernel<12, 80>" in text          # 12 waves
+    # a 12-wave, 80-wide instantiation, launched with 64 threads per wave
+    assert "launch_attention<12, 80, 192>(" in text and "(attention_kernel<TW, D, TR>), dim3(heads, B), dim3(64 * TW)," in text
     m = re.search(r"constexpr int attention_lds_bytes\(\) \{\s*return 4 \* \((.*?)\);", text, re.S)
     assert m, "attention_lds_bytes() not found"
-    TW, D = 12, 80
-    assert 2 * 4 * max(16 * TW * (D + 4), D * (16 * TW + 4)) <= 160 * 1024       # two workgroups' LDS fit a CU
+    lds_bytes = lambda TW, D: 4 * max(16 * TW * (D + 4), D * (16 * TW + 4))
+    assert m.group(1).split("//")[0].replace(" ", "") == "16*TW*(D+4)>D*(16*TW+4)?16*TW*(D+4):D*(16*TW+4)"     # = lds_bytes
+    assert 2 * lds_bytes(12, 80) <= 160 * 1024       # two workgroups' LDS fit a CU
+    b = next(b for b in blocks if "attention_kernelILi13ELi64ELi197E" in b.split()[0])
+    regs = field(b, r" VGPRs: (\d+)") + field(b, r"AGPRs: (\d+)")
+    spill, scratch = field(b, r"VGPRs Spill: (\d+)"), field(b, r"ScratchSize \[bytes/lane\]: (\d+)")
+    occ = field(b, r"Occupancy \[waves/SIMD\]: (\d+)")
+    assert regs <= 128 and occ >= 4 and spill == 0 and scratch == 0, (regs, occ, spill, scratch)
+    assert "launch_attention<13, 64, 197>(" in text and lds_bytes(13, 64) <= 65536

@@ -85,6 +85,24 @@ def test_attention_197x64_masked_keys_carry_no_weight():
     assert err < 5e-6, err
 
 
+def test_attention_192x80_writes_its_rows_and_is_batch_independent():
+    """(B, T, heads, D) = (3, 192, 2, 80): the ViT-H instantiation of the kernel body the 197-token tests run, through the same
+    harness.  B = 3 exercises the row stride of a later crop, heads = 2 the head stride.  Every element written and finite, the 16
+    guard rows behind the last crop untouched, the 5e-6 bar of the ViT-H test, and crop 1 alone equal to crop 1 of the batch bit
+    for bit."""
+    g = torch.Generator().manual_seed(6)
+    B, T, heads, D = 3, 192, 2, 80
+    qkv = torch.randn(B, T, 3 * heads * D, generator=g)
+    ref = _attention_ref(qkv, heads, D)
+    out, guard = _run_attention(qkv, heads, D)
+    assert torch.isfinite(out).all() and torch.isnan(guard).all()
+    err = (out.double() - ref).abs().max().item()
+    print(f"attention 192x80: max abs err {err:.3e}")
+    assert err < 5e-6, err
+    one, guard = _run_attention(qkv[1:2], heads, D)
+    assert torch.isnan(guard).all() and torch.equal(one[0], out[1])
+
+
 def test_layernorm_768_vs_torch():
     """The form and bar of test_gpu_hamer.test_layernorm_vs_torch for C = 768 (returned HANDS_EINVAL before)."""
     L = _lib.lib()
@@ -134,6 +152,26 @@ def test_tail_layernorm_avgpool_vs_torch():
     err = (o[:B * 49].view(B, 7, 7, C).double() - ref).abs().max().item()
     print(f"tail: max abs err {err:.3e}")
     assert err < 2e-5 and torch.isnan(o[B * 49:]).all()
+
+
+def test_tail_equals_layernorm_then_window_average_bitwise():
+    """hands_vit_tail_f32 against hands_layernorm_f32, bit for bit: both normalise a row with the same routine, so LayerNorm of all
+    B * 17 rows, then ((r00 + r01) + (r10 + r11)) * 0.25 in fp32 on the CPU over each 2x2 window of tokens 1..16, is the tail
+    kernel's output exactly.  G = 4 is the smallest even grid with more than one window per row."""
+    L = _lib.lib()
+    g = torch.Generator().manual_seed(7)
+    B, G, C, eps = 2, 4, 768, 1e-6
+    x = 3 * torch.randn(B, 1 + G * G, C, generator=g) + 0.5
+    gam, bet = torch.randn(C, generator=g), torch.randn(C, generator=g)
+    d = [t.to(DEV) for t in (x, gam, bet)]
+    ln = torch.empty(B * (1 + G * G), C, device=DEV)
+    check(L.hands_layernorm_f32(ptr(d[0]), ptr(d[1]), ptr(d[2]), ptr(ln), None, 1, B * (1 + G * G), C, eps, _stream()), "layernorm")
+    tail = torch.empty(B, G // 2, G // 2, C, device=DEV)
+    check(L.hands_vit_tail_f32(ptr(d[0]), ptr(d[1]), ptr(d[2]), ptr(tail), B, G, C, eps, _stream()), "vit_tail")
+    torch.cuda.synchronize()
+    r = ln.cpu().view(B, 1 + G * G, C)[:, 1:].reshape(B, G // 2, 2, G // 2, 2, C)      # (b, oy, dy, ox, dx, c)
+    ref = ((r[:, :, 0, :, 0] + r[:, :, 0, :, 1]) + (r[:, :, 1, :, 0] + r[:, :, 1, :, 1])) * 0.25
+    assert ref.dtype == torch.float32 and torch.equal(tail.cpu(), ref)
 
 
 # ---- the trunk and the forward ------------------------------------------------------------------------------------------------

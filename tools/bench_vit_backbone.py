@@ -6,8 +6,8 @@
   2. one-stream pass (``overlap_trunks = False``) with every GEMM / convolution launch and every attention call bracketed by
      events: the GEMMs' algorithmic FLOP rate as a fraction of the fp32-MFMA peak (157.3 TFLOP/s), the attention kernel's time
      per call and its share of the forward;
-  3. the attention kernels alone, same box, same run: attention_pad_kernel<13,64,197> (ViT-B/16: 197 tokens, 12 heads x 64, one
-     call of the hand job = 2 bz crops) next to attention_kernel<12,80> (ViT-H/16 of hamer_light: 192 tokens, 16 heads x 80, 128
+  3. the attention kernels alone, same box, same run: attention_kernel<13,64,197> (ViT-B/16: 197 tokens, 12 heads x 64, one
+     call of the hand job = 2 bz crops) next to attention_kernel<12,80,192> (ViT-H/16 of hamer_light: 192 tokens, 16 heads x 80, 128
      crops = its bz 64 test shape), each as algorithmic GFLOP/s (4 T^2 D per head and crop).
 
 Recipe weights, synthetic inputs; events only, no profiler.  Prints one JSON line."""

@@ -40,7 +40,7 @@ def stamp(array, slot, cond="prof"):
 
 def conv_tile_timeline():
     s = open(CONV).read()
-    s = sub(s, "namespace {\n\ntypedef float f32x16", """__device__ unsigned long long g_prof[16384 * 8];
+    s = sub(s, "namespace {\n\ntypedef unsigned int u32x4", """__device__ unsigned long long g_prof[16384 * 8];
 __device__ unsigned long long g_steps[64 * 256];
 extern "C" int hands_debug_prof(void* dst, void* dst2) {
   hipDeviceSynchronize();
@@ -50,7 +50,7 @@ extern "C" int hands_debug_prof(void* dst, void* dst2) {
 }
 namespace {
 
-typedef float f32x16""", "globals")
+typedef unsigned int u32x4""", "globals")
     s = sub(s, "  LOAD_TILES(kt0);\n  STORE_TILES(0);\n  __syncthreads();\n",
             "  const bool prof = threadIdx.x == 0 && blockIdx.x < 16384;\n  " + stamp("g_prof", 1) +
             "\n  LOAD_TILES(kt0);\n  STORE_TILES(0);\n  __syncthreads();\n  " + stamp("g_prof", 2) + "\n", "prologue")
@@ -68,7 +68,7 @@ typedef float f32x16""", "globals")
 
 def conv_clock():
     s = open(CONV).read()
-    s = sub(s, "namespace {\n\ntypedef float f32x16", """__device__ unsigned long long g_prof[32768 * 4];
+    s = sub(s, "namespace {\n\ntypedef unsigned int u32x4", """__device__ unsigned long long g_prof[32768 * 4];
 extern "C" int hands_debug_prof(void* dst, void* dst2) {
   hipDeviceSynchronize();
   hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_prof), sizeof(unsigned long long) * 32768 * 4);
@@ -76,7 +76,7 @@ extern "C" int hands_debug_prof(void* dst, void* dst2) {
 }
 namespace {
 
-typedef float f32x16""", "globals")
+typedef unsigned int u32x4""", "globals")
     s = sub(s, "  const int ntiles = a.nblk_m * a.nblk_n;\n  const int split = a.ksplit > 1 ? blockIdx.x / ntiles : 0;\n",
             "  if (threadIdx.x == 0 && blockIdx.x < 32768) { g_prof[blockIdx.x * 4 + 0] = __builtin_amdgcn_s_memrealtime(); "
             "g_prof[blockIdx.x * 4 + 1] = __builtin_amdgcn_s_memtime(); }\n"
@@ -90,7 +90,7 @@ typedef float f32x16""", "globals")
 
 def conv_ring():
     s = open(CONV).read()
-    s = sub(s, "namespace {\n\ntypedef float f32x16", """__device__ unsigned long long g_ring[8192 * 4];
+    s = sub(s, "namespace {\n\ntypedef unsigned int u32x4", """__device__ unsigned long long g_ring[8192 * 4];
 __device__ unsigned int g_n;
 extern "C" int hands_debug_ring(void* dst, unsigned int* n, int reset) {
   hipDeviceSynchronize();
@@ -101,7 +101,7 @@ extern "C" int hands_debug_ring(void* dst, unsigned int* n, int reset) {
 }
 namespace {
 
-typedef float f32x16""", "globals")
+typedef unsigned int u32x4""", "globals")
     s = sub(s, "  const int ntiles = a.nblk_m * a.nblk_n;\n  const int split = a.ksplit > 1 ? blockIdx.x / ntiles : 0;\n",
             "  unsigned long long rt0 = 0, mt0 = 0;\n  const bool stamp = threadIdx.x == 0 && blockIdx.x == gridDim.x / 2;\n"
             "  if (stamp) { rt0 = __builtin_amdgcn_s_memrealtime(); mt0 = __builtin_amdgcn_s_memtime(); }\n"
@@ -136,7 +136,7 @@ def wino_phases():
     """conv_wino: s_memtime (shader cycles) of wave 0 at entry / before the first barrier / after it / at exit, plus the
     summed duration of the per-channel-block epilogues (tools/prof_wino.py)"""
     s = open(WINO).read()
-    s = sub(s, "namespace {\n\ntypedef float f32x16", """__device__ unsigned long long g_wprof[32768 * 8];
+    s = sub(s, "namespace {\n\ntypedef unsigned int u32x4", """__device__ unsigned long long g_wprof[32768 * 8];
 extern "C" int hands_debug_wprof(void* dst) {
   hipDeviceSynchronize();
   hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_wprof), sizeof(unsigned long long) * 32768 * 8);
@@ -151,7 +151,7 @@ extern "C" int hands_debug_wprof_clear() {
 }
 namespace {
 
-typedef float f32x16""", "globals")
+typedef unsigned int u32x4""", "globals")
     st = ("__builtin_amdgcn_sched_barrier(0); if (threadIdx.x == 0 && blockIdx.x < 32768) g_wprof[blockIdx.x * 8 + %d] = "
           "__builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0);")
     s = sub(s, "  const int tid = threadIdx.x;\n  const int lane = tid & 63;\n  const int xi =", "  " + st % 0 +
@@ -168,7 +168,7 @@ typedef float f32x16""", "globals")
 
 
 def attn_phases():
-    """attention_kernel<12,80> (ViT self-attention, csrc/transformer.hip): s_memrealtime of lane 0 of EVERY wave at entry / after
+    """attention_kernel<TW,D,TR> (ViT self-attention, csrc/transformer.hip; both instantiations): s_memrealtime of lane 0 of EVERY wave at entry / after
     the K fill's barrier / after Q.K^T / after the V^T write / after the softmax / after the barrier / after P.V + stores;
     slot 7 = HW_ID | XCC_ID << 32 (tools/prof_attn.py)"""
     s = open(TRANS).read()
@@ -184,15 +184,15 @@ namespace {
     head, body = s[:i], s[i:]
     st = ("__builtin_amdgcn_sched_barrier(0); if ((threadIdx.x & 63) == 0 && pslot < 32768) g_aprof[pslot * 8 + %d] = "
           "__builtin_amdgcn_s_memrealtime(); __builtin_amdgcn_sched_barrier(0);")
-    body = sub(body, "  const float* base = qkv + (long long)b * T * 3 * C + h * D;\n",
-               "  const float* base = qkv + (long long)b * T * 3 * C + h * D;\n"
+    body = sub(body, "  const float* base = qkv + (long long)b * TR * 3 * C + h * D;\n",
+               "  const float* base = qkv + (long long)b * TR * 3 * C + h * D;\n"
                "  const int pslot = (blockIdx.y * gridDim.x + blockIdx.x) * TW + (threadIdx.x >> 6);\n  " + st % 0 + "\n", "entry")
     body = sub(body, "  __syncthreads();\n  // V: requested now", "  __syncthreads();\n  " + st % 1 + "\n  // V: requested now", "K fill")
     body = sub(body, "  __syncthreads();   // every wave is done with K\n", "  " + st % 2 + "\n  __syncthreads();   // every wave is done with K\n", "QK")
     body = sub(body, "  // softmax over the keys of this lane's query", "  " + st % 3 + "\n  // softmax over the keys of this lane's query", "V write")
     body = sub(body, "  __syncthreads();   // V^T complete\n", "  " + st % 4 + "\n  __syncthreads();   // V^T complete\n  " + st % 5 + "\n", "softmax")
-    body = sub(body, "    *reinterpret_cast<float4*>(orow + db * 16) = make_float4(o[db][0], o[db][1], o[db][2], o[db][3]);\n}\n",
-               "    *reinterpret_cast<float4*>(orow + db * 16) = make_float4(o[db][0], o[db][1], o[db][2], o[db][3]);\n  " + st % 6 +
+    body = sub(body, "      *reinterpret_cast<float4*>(orow + db * 16) = make_float4(o[db][0], o[db][1], o[db][2], o[db][3]);\n  }\n}\n",
+               "      *reinterpret_cast<float4*>(orow + db * 16) = make_float4(o[db][0], o[db][1], o[db][2], o[db][3]);\n  }\n  " + st % 6 +
                "\n  if ((threadIdx.x & 63) == 0 && pslot < 32768) g_aprof[pslot * 8 + 7] = "
                "(unsigned long long)__builtin_amdgcn_s_getreg(4 | (31 << 11)) | ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32);\n}\n", "exit")
     return head + body, "transformer.hip"
