@@ -123,6 +123,10 @@ SIGNATURES = {
     "hands_rot6d_to_matrix_cols_f32": [_P, _I, _P, _I, _P],
     "hands_vit_tokens_f32": [_P, _P, _P, _P, _I, _I, _I, _P],
     "hands_vit_tail_f32": [_P, _P, _P, _P, _I, _I, _I, _F, _P],
+    "hands_wide_attention_f32": [_P, C.c_longlong, _I, _P, C.c_longlong, _I, _P, C.c_longlong, _I, _P, C.c_longlong, _I,
+                                 _I, _I, _I, _I, _F, _P],
+    "hands_vector_tokens_f32": [_P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P],
+    "hands_token_mean_f32": [_P, _P, _I, _I, _I, _P],
     "hands_upsample_bilinear_add_f32": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "hands_pool2x2_nhwc_f32": [_P, _P, _I, _I, _I, _I, _I, _P],
     "hands_channel_pool_f32": [_P, _P, C.c_longlong, _I, _P],

@@ -24,12 +24,18 @@ statement of ``forward`` runs as a hand-written gfx950 kernel from ``libhands_hi
                                               embedding), hands_layernorm_f32 (C = 768), hands_attention_f32 (197 tokens, 12 x 64),
                                               hands_vit_tail_f32 (encoder.ln + AvgPool2d(2)), vit_conv as one folded 3x3 layer
 
+    hmr_layer.py:17-42, 67-86  transformer head (tf_decoder=True)   hands_vector_tokens_f32 (109 scalar tokens), hands_wide_attention_f32
+                                              (one head of dimension 1024: tokens x tokens, tokens x 49 pixels), hands_token_mean_f32,
+                                              every Linear on hands_conv2d_nhwc_f32 (bias / ReLU / residual epilogue); feature_conv
+                                              is not run
+
 torch is used for parameter containers, device buffers and streams only.  Built configurations: backbones resnet50 and vit_b_16,
 tf_decoder=False with every pos_enc of model.py -- 'center+corner_latent' (shipped default), 'sinusoidal_cc', 'center', 'corner',
 'center+corner', 'dense', 'dense_latent', 'cam_conv', 'pcl', 'perspective_correction', None -- ``no_crops`` (arctic_light), the
 grasp head with / without the global feature vector or absent, ``separate_hands``, ``regress_center_corner``,
-``use_glb_feat=False``, ``use_depth_loss`` (the depth head); tf_decoder, backbone='resnet18' and the renderer switch raise
-``NotImplementedError``.
+``use_glb_feat=False``, ``use_depth_loss`` (the depth head); the constructor keyword tf_decoder=True with pos_enc 'center+corner_latent', 'dense_latent' or
+None (the reference itself fails on tf_decoder with 'sinusoidal_cc', 'cam_conv', ``no_crops`` or ``regress_center_corner``);
+backbone='resnet18' and the renderer switch raise ``NotImplementedError``.
 """
 from __future__ import annotations
 
@@ -103,14 +109,72 @@ class _HMRLayerParams(nn.Module):
         self.decoders = nn.ModuleDict({k: nn.Linear(mid_dim, v) for k, v in specs.items()})
 
 
-class HandHMR(nn.Module):
-    """hand_hmr.py:9-44 parameter layout."""
+class _MHAParams(nn.Module):
+    """nn.MultiheadAttention's parameter layout (packed in_proj rows [q | k | v], out_proj as a Linear)."""
 
-    def __init__(self, feat_dim, is_rhand, n_iter):
+    def __init__(self, dim):
+        super().__init__()
+        self.in_proj_weight = nn.Parameter(torch.empty(3 * dim, dim))
+        self.in_proj_bias = nn.Parameter(torch.zeros(3 * dim))
+        self.out_proj = nn.Linear(dim, dim)
+        nn.init.xavier_uniform_(self.in_proj_weight)
+
+
+class _TFLayerParams(nn.Module):
+    """hands_light/transformer.py:398-415 (encoder layer) / :601-622 (decoder layer: + multihead_attn, norm3).  The norms are
+    never applied (the head runs both layers with no_norm=True) but stay in the state_dict, as in the reference."""
+
+    def __init__(self, dim, cross):
+        super().__init__()
+        self.self_attn = _MHAParams(dim)
+        if cross:
+            self.multihead_attn = _MHAParams(dim)
+        self.linear1 = nn.Linear(dim, dim)
+        self.linear2 = nn.Linear(dim, dim)
+        self.norm1 = nn.LayerNorm(dim)
+        self.norm2 = nn.LayerNorm(dim)
+        if cross:
+            self.norm3 = nn.LayerNorm(dim)
+
+
+class _TFStack(nn.Module):
+    """TransformerDecoder / TransformerEncoder with num_layers=1: ``layers.0``."""
+
+    def __init__(self, dim, cross):
+        super().__init__()
+        self.layers = nn.ModuleList([_TFLayerParams(dim, cross)])
+
+
+class _HMRLayerTFParams(nn.Module):
+    """hmr_layer.py:7-62 with tf_decoder=True: ``refine`` is replaced by the token embeddings, one decoder layer over the
+    feature pixels and one encoder layer; ``in_dim`` is the channel count of the map the head reads."""
+
+    def __init__(self, in_dim, mid_dim, specs):
+        super().__init__()
+        self.vector_mlp = nn.Sequential(nn.Linear(1, mid_dim), nn.ReLU())
+        self.feat_mlp = nn.Sequential(nn.Linear(in_dim, mid_dim), nn.ReLU())
+        self.refine_decoder = _TFStack(mid_dim, cross=True)
+        self.self_attn = _TFStack(mid_dim, cross=False)
+        self.decoders = nn.ModuleDict({k: nn.Linear(mid_dim, v) for k, v in specs.items()})
+
+
+TF_TOKENS = 109      # one token per scalar of the vectors, in `init_vector_dict` order: pose_6d 96, shape 10, cam_t/wp 3
+TF_DIM = 1024        # d_model of the head's layers = its single head's dimension
+TF_PASS = 256        # samples per pass of the transformer head (the (109 n, 3072) in_proj output of 256 samples is 343 MB)
+
+
+class HandHMR(nn.Module):
+    """hand_hmr.py:9-44 parameter layout.  ``tf_in``: tf_decoder=True, the head reads a (tf_in, 7, 7) map."""
+
+    def __init__(self, feat_dim, is_rhand, n_iter, tf_in=None):
         super().__init__()
         self.is_rhand, self.n_iter = is_rhand, n_iter
         self.hand_specs = {"pose_6d": 96, "cam_t/wp": 3, "shape": 10}
-        self.hmr_layer = _HMRLayerParams(feat_dim, 1024, self.hand_specs)
+        if tf_in is None:
+            self.hmr_layer = _HMRLayerParams(feat_dim, 1024, self.hand_specs)
+        else:
+            self.hmr_layer = _HMRLayerTFParams(tf_in, TF_DIM, self.hand_specs)
+            self.cam_init_precursor = nn.Sequential(nn.Linear(tf_in, feat_dim), nn.ReLU())
         self.cam_init = nn.Sequential(nn.Linear(feat_dim, 512), nn.ReLU(), nn.Linear(512, 512), nn.ReLU(),
                                       nn.Linear(512, 3))
 
@@ -277,7 +341,7 @@ class _PackedHolder:
 
 class HandsLight(EngineSwitches, nn.Module):
     def __init__(self, backbone="resnet50", focal_length=1000.0, img_res=224, args=None,
-                 mano_assets=None):
+                 mano_assets=None, tf_decoder=False):
         super().__init__()
         self.engine = ConvEngine()
         # Winograd F(4x4,3x3) (csrc/conv_wino4.hip, 2.25 multiplications per output) for the stride-1 3x3 convolutions of these
@@ -320,9 +384,29 @@ class HandsLight(EngineSwitches, nn.Module):
         self.separate_hands = bool(get("separate_hands", False))       # model.py:40-50: own trunk weights per side
         self.regress_center_corner = bool(get("regress_center_corner", False))   # model.py:157-172, 426-433
         self.use_glb_feat = bool(get("use_glb_feat", False))
+        # tf_decoder (model.py:34-38, 312-314): feature_conv is skipped and both heads read the concatenated 7x7 map through the
+        # transformer head (hmr_layer.py:17-42, 67-86) -- :meth:`_tf_head`
+        # The switch is the constructor's keyword ``tf_decoder=True``, like ``backbone``.  ``args.tf_decoder`` alone keeps raising
+        # NotImplementedError, as it always has here: a caller who hands over the reference's args gets the head only by asking
+        # for it by name.
+        self.tf_decoder = bool(tf_decoder)
+        self.tf_pass = TF_PASS     # samples per pass of the transformer head (results do not depend on it)
+        tf = self.tf_decoder
         unsupported = {
             f"pos_enc={pos_enc!r}": self.enc_mode is None,
-            "tf_decoder": bool(get("tf_decoder", False)),
+            # the reference itself fails on these: feat_mlp / cam_init_precursor are built feat_dim wide for every encoding but
+            # 'center+corner_latent' and 'dense_latent' (hmr_layer.py:26-31, hand_hmr.py:22-27) and then meet the 2128 / 2054
+            # channel map ("mat1 and mat2 shapes cannot be multiplied"); the pooled vector of no_crops has no (h, w) to unpack
+            # (hmr_layer.py:74); center_head meets the 4-D map (model.py:431)
+            "args.tf_decoder (the transformer head is built: ask for it with HandsLight(..., tf_decoder=True))":
+                bool(get("tf_decoder", False)) and not tf,
+            "tf_decoder with sinusoidal_cc": tf and pos_enc == "sinusoidal_cc",
+            "tf_decoder with cam_conv": tf and pos_enc == "cam_conv",
+            "tf_decoder with no_crops": tf and self.no_crops,
+            "tf_decoder with regress_center_corner": tf and self.regress_center_corner,
+            # runs in the reference, not checked against it here: no fixture
+            f"tf_decoder with pos_enc={pos_enc!r} (checked: 'center+corner_latent', 'dense_latent', None)":
+                tf and pos_enc not in ("center+corner_latent", "dense_latent", None, "sinusoidal_cc", "cam_conv"),
             "use_depth_loss with no_crops": self.use_depth_loss and self.no_crops,      # `depth_r` undefined in the reference (:308-310, 422)
             "use_render_seg_loss (call hands_amd.MANORenderer on the output instead)": bool(get("use_render_seg_loss", False)),
             # the reference itself fails on these combinations (`features` / `feat_vec` undefined, model.py:191-201, 402-404;
@@ -361,11 +445,12 @@ class HandsLight(EngineSwitches, nn.Module):
             self.hand_backbone = Trunk(3 + self.enc_channels)
             if vit:
                 self.hand_backbone_vit_conv = vit_conv_params()
-        self.head_r = HandHMR(feat_dim, True, 3)
-        self.head_l = HandHMR(feat_dim, False, 3)
         self.latent_channels = (5 * 4 * self.n_freq if self.enc_mode == "latent" else 4 * self.n_freq if pos_enc == "dense_latent" else
                                 6 if pos_enc == "cam_conv" else 0)
         fc_dim = feat_dim + self.latent_channels                                           # model.py:79-88
+        # (tf_decoder: feat_mlp and cam_init_precursor take the concatenated map, hmr_layer.py:26-31 / hand_hmr.py:22-27)
+        self.head_r = HandHMR(feat_dim, True, 3, tf_in=fc_dim if tf else None)
+        self.head_l = HandHMR(feat_dim, False, 3, tf_in=fc_dim if tf else None)
         self.feature_conv = nn.Sequential(
             nn.Conv2d(fc_dim, 1024, 1, bias=False), nn.ReLU(inplace=True),
             nn.Conv2d(1024, 512, 3, bias=False), nn.ReLU(inplace=True),
@@ -504,11 +589,35 @@ class HandsLight(EngineSwitches, nn.Module):
         P["ci0"] = pack_linear(cpu(ci[0].weight), cpu(ci[0].bias), dev)
         P["ci2"] = pack_linear(cpu(ci[2].weight), cpu(ci[2].bias), dev)
         P["ci4"] = pack_linear(cpu(ci[4].weight), cpu(ci[4].bias), dev, n_total=4)
-        rf = head.hmr_layer.refine
-        P["r0"] = pack_linear(cpu(rf[0].weight), cpu(rf[0].bias), dev, col_index=hmr_state_columns(F),
-                              k_total=F + HMR_VEC)
-        P["r3"] = pack_linear(cpu(rf[3].weight), cpu(rf[3].bias), dev)
-        d = head.hmr_layer.decoders
+        hl = head.hmr_layer
+        if self.tf_decoder:
+            # every Linear of the transformer head as a pointwise GEMM; the cross-attention in_proj is cut into its query rows
+            # (applied to the tokens, every iteration) and its key | value rows (applied to `memory`, once per forward)
+            lin = lambda m: pack_linear(cpu(m.weight), cpu(m.bias), dev)
+            E = TF_DIM
+            dl, el = hl.refine_decoder.layers[0], hl.self_attn.layers[0]
+            xw, xb = cpu(dl.multihead_attn.in_proj_weight), cpu(dl.multihead_attn.in_proj_bias)
+            P["tf"] = {
+                "pre": lin(head.cam_init_precursor[0]), "feat_mlp": lin(hl.feat_mlp[0]),
+                "vec_w": cpu(hl.vector_mlp[0].weight).float().reshape(E).contiguous().to(dev),
+                "vec_b": cpu(hl.vector_mlp[0].bias).float().contiguous().to(dev),
+                "d_qkv": pack_linear(cpu(dl.self_attn.in_proj_weight), cpu(dl.self_attn.in_proj_bias), dev),
+                "d_proj": lin(dl.self_attn.out_proj),
+                "x_q": pack_linear(xw[:E], xb[:E], dev), "x_kv": pack_linear(xw[E:], xb[E:], dev),
+                "x_proj": lin(dl.multihead_attn.out_proj), "d_l1": lin(dl.linear1), "d_l2": lin(dl.linear2),
+                "e_qkv": pack_linear(cpu(el.self_attn.in_proj_weight), cpu(el.self_attn.in_proj_bias), dev),
+                "e_proj": lin(el.self_attn.out_proj), "e_l1": lin(el.linear1), "e_l2": lin(el.linear2)}
+            # cam_t.wp.init = 1 + an O(0.1) read-out: its error is the final rounding plus what the four layers in front of it
+            # pass on.  The reference's fp32 value is within 0.3-0.8 ulp of its fp64 run, so the layers are accumulated in fp64
+            # (HANDS_ACC_F64: correctly rounded fp32 outputs; the precursor is 4 % of the head's work at half the matrix rate)
+            for pc in (P["tf"]["pre"], P["ci0"], P["ci2"], P["ci4"]):
+                pc.acc64 = True
+        else:
+            rf = hl.refine
+            P["r0"] = pack_linear(cpu(rf[0].weight), cpu(rf[0].bias), dev, col_index=hmr_state_columns(F),
+                                  k_total=F + HMR_VEC)
+            P["r3"] = pack_linear(cpu(rf[3].weight), cpu(rf[3].bias), dev)
+        d = hl.decoders
         wd = torch.cat([cpu(d["pose_6d"].weight), cpu(d["shape"].weight), cpu(d["cam_t/wp"].weight)], 0)
         bd = torch.cat([cpu(d["pose_6d"].bias), cpu(d["shape"].bias), cpu(d["cam_t/wp"].bias)], 0)
         rows = list(range(96)) + [96 + i for i in range(10)] + [108 + i for i in range(3)]
@@ -538,8 +647,9 @@ class HandsLight(EngineSwitches, nn.Module):
                          pack_linear(cpu(head[4].weight), cpu(head[4].bias), dev, n_total=8)]
         fc = self.feature_conv
         # 'dense_latent' / 'cam_conv': the concatenated map is stored with its channel count padded to a multiple of 16 (zeros)
-        P["fc0"] = pack_conv(cpu(fc[0].weight), None, 1, 0, dev,
-                             cin_pad_to=self._cat_ld() if self.enc_mode == "dense_latent" else None)
+        if not self.tf_decoder:      # (tf_decoder: feature_conv keeps its parameters and is never run, model.py:312-314)
+            P["fc0"] = pack_conv(cpu(fc[0].weight), None, 1, 0, dev,
+                                 cin_pad_to=self._cat_ld() if self.enc_mode == "dense_latent" else None)
         if self.use_depth_loss:
             dm = self.depth_mlp
             P["depth"] = [pack_conv(cpu(dm[i].weight), cpu(dm[i].bias), 1, 1, dev,
@@ -547,11 +657,12 @@ class HandsLight(EngineSwitches, nn.Module):
             lin = torch.linspace(-1, 1, 7)                                # model.py:172-175 (`init_grid`, 'ij' meshgrid)
             xg, yg = torch.meshgrid(lin, lin, indexing="ij")
             P["depth_grid"] = torch.stack([xg, yg], dim=-1).reshape(49, 2).contiguous().to(dev)
-        P["fc2"] = pack_conv(cpu(fc[2].weight), None, 1, 0, dev)
-        P["fc4"] = pack_conv(cpu(fc[4].weight), None, 1, 0, dev)
-        # nn.Flatten on NCHW (B,256,3,3): reference column c*9 + hw; NHWC buffer column hw*256 + c
-        col = [(k % 9) * 256 + (k // 9) for k in range(256 * 9)]
-        P["fc7"] = pack_linear(cpu(fc[7].weight), cpu(fc[7].bias), dev, col_index=col)
+        if not self.tf_decoder:
+            P["fc2"] = pack_conv(cpu(fc[2].weight), None, 1, 0, dev)
+            P["fc4"] = pack_conv(cpu(fc[4].weight), None, 1, 0, dev)
+            # nn.Flatten on NCHW (B,256,3,3): reference column c*9 + hw; NHWC buffer column hw*256 + c
+            col = [(k % 9) * 256 + (k // 9) for k in range(256 * 9)]
+            P["fc7"] = pack_linear(cpu(fc[7].weight), cpu(fc[7].bias), dev, col_index=col)
         if self.use_grasp_loss:
             g = self.grasp_classifier
             Fg = F if self.use_glb_feat_w_grasp else 0
@@ -910,6 +1021,75 @@ class HandsLight(EngineSwitches, nn.Module):
             out[lo:lo + n] = x[: n * h * w * 4].view(n, h, w, 4)[..., 0]      # Cout = 1 stored with a pixel stride of 4 floats
         return out[:bz], out[bz:]
 
+    def _tf_head(self, L, hp, dev, stream, side, bz, HW, cat, state, caminit4):
+        """``HandHMR.forward(features, use_pool=False)`` with tf_decoder=True (hand_hmr.py:57-62, 73-92; hmr_layer.py:67-86) for one
+        hand: rows [side bz, (side + 1) bz) of the concatenated map ``cat`` (B2, HW, Cc) -> the vector columns of its ``state``
+        rows (ld 112) and its ``caminit4`` rows.
+
+          cam_init_precursor per pixel (GEMM + ReLU) -> average pool -> cam_init MLP -> hands_hmr_init_f32
+          memory = feat_mlp(pixels) and the cross-attention k | v = in_proj[E:](memory): ONCE, they do not change between iterations
+          3 x [ hands_vector_tokens_f32 (109 tokens) -> decoder layer: self-attention, cross-attention, FFN -> encoder layer:
+                self-attention, FFN -> hands_token_mean_f32 -> decoders GEMM + residual on the vectors ]
+
+        Every residual is the GEMM's epilogue (x = x + f(x), no norm: no_norm=True); attention is hands_wide_attention_f32 reading
+        the packed in_proj output in place.  Samples are walked in passes of ``tf_pass`` (256) so that the workspaces stop growing at
+        bz = 256; every kernel's rows are per sample, so a sample's result does not depend on the pass it falls in."""
+        T, E, F, Cc = TF_TOKENS, TF_DIM, self.feat_dim, self._cat_ld() if self.enc_mode in ("latent", "dense_latent") else self.feat_dim
+        tf = hp["tf"]
+        assert tf["feat_mlp"].Cin == Cc and tf["pre"].Cin == Cc
+        cap = min(bz, self.tf_pass)
+        buf = lambda nm, numel: self._buf(f"tf_{nm}{side}", numel, dev)
+        mem, kv, pre, pooled = buf("mem", cap * HW * E), buf("kv", cap * HW * 2 * E), buf("pre", cap * HW * F), buf("pool", cap * F)
+        h512a, h512b = buf("h512a", cap * 512), buf("h512b", cap * 512)
+        x, att, q, hid = buf("x", cap * T * E), buf("att", cap * T * E), buf("q", cap * T * E), buf("hid", cap * T * E)
+        qkv, xc = buf("qkv", cap * T * 3 * E), buf("xc", cap * E)
+        scale = float(E) ** -0.5
+        conv = self.engine.conv
+
+        def attention(qb, kb, koff, ldk, Tk, n):
+            """softmax(scale q k^T) v: q rows of ``qb`` (ld of its own width), k | v side by side in ``kb`` from column ``koff``"""
+            ldq = 3 * E if qb is kb else E
+            check(L.hands_wide_attention_f32(ptr(qb), T * ldq, ldq, ptr(kb, koff), Tk * ldk, ldk, ptr(kb, koff + E), Tk * ldk, ldk,
+                                             ptr(att), T * E, E, n, T, Tk, E, scale, stream), "wide_attention")
+
+        for lo in range(0, bz, self.tf_pass):
+            n = min(self.tf_pass, bz - lo)
+            r0 = side * bz + lo                       # first row of the pass in the (B2, ..) buffers
+            so, co, M = r0 * HMR_VEC, r0 * 4, n * T
+            # -- init_vector_dict (hand_hmr.py:46-71): cam_init_precursor per pixel BEFORE the average pool
+            conv(L, tf["pre"], cat, n * HW, 1, 1, pre, True, stream, x_off=r0 * HW * Cc)
+            check(L.hands_avgpool_nhwc_f32(ptr(pre), ptr(pooled), n, HW, F, F, stream), "avgpool")
+            conv(L, hp["ci0"], pooled, n, 1, 1, h512a, True, stream, splitk=True)
+            conv(L, hp["ci2"], h512a, n, 1, 1, h512b, True, stream, splitk=True)
+            conv(L, hp["ci4"], h512b, n, 1, 1, caminit4, False, stream, out_off=co)
+            check(L.hands_hmr_init_f32(ptr(state, so), ptr(caminit4, co), n, HMR_VEC, 0, stream), "hmr_init")
+            # -- memory and the cross-attention keys | values
+            conv(L, tf["feat_mlp"], cat, n * HW, 1, 1, mem, True, stream, x_off=r0 * HW * Cc)
+            conv(L, tf["x_kv"], mem, n * HW, 1, 1, kv, False, stream)
+            for _ in range(3):
+                # tokens in `init_vector_dict` order: pose_6d 96, shape 10 (state columns 0..105), cam_t/wp 3 (columns 108..110)
+                check(L.hands_vector_tokens_f32(ptr(state, so), HMR_VEC, 106, 2, ptr(tf["vec_w"]), ptr(tf["vec_b"]), ptr(x), n, T, E,
+                                                stream), "vector_tokens")
+                # decoder layer (transformer.py:652-658): self-attention, cross-attention over the pixels, FFN
+                conv(L, tf["d_qkv"], x, M, 1, 1, qkv, False, stream)
+                attention(qkv, qkv, E, 3 * E, T, n)
+                conv(L, tf["d_proj"], att, M, 1, 1, x, False, stream, res=x)
+                conv(L, tf["x_q"], x, M, 1, 1, q, False, stream)
+                attention(q, kv, 0, 2 * E, HW, n)
+                conv(L, tf["x_proj"], att, M, 1, 1, x, False, stream, res=x)
+                conv(L, tf["d_l1"], x, M, 1, 1, hid, True, stream)
+                conv(L, tf["d_l2"], hid, M, 1, 1, x, False, stream, res=x)
+                # encoder layer (transformer.py:533-539): self-attention, FFN
+                conv(L, tf["e_qkv"], x, M, 1, 1, qkv, False, stream)
+                attention(qkv, qkv, E, 3 * E, T, n)
+                conv(L, tf["e_proj"], att, M, 1, 1, x, False, stream, res=x)
+                conv(L, tf["e_l1"], x, M, 1, 1, hid, True, stream)
+                conv(L, tf["e_l2"], hid, M, 1, 1, x, False, stream, res=x)
+                # token mean, then the three decoders' residual update of the vectors (hmr_layer.py:78, 82-83)
+                check(L.hands_token_mean_f32(ptr(x), ptr(xc), n, T, E, stream), "token_mean")
+                conv(L, hp["dec"], xc, n, 1, 1, state, False, stream, res=state, out_ps=HMR_VEC, res_ps=HMR_VEC, out_off=so,
+                     res_off=so, splitk=True)
+
     def _forward_tail(self, L, P, dev, main, bz, fh, fw, featg, feath, center, corner, K, flipped, dense_enc=None, rot_in=None):
         """Everything after the trunks (model.py:196-411), enqueued on ``main`` (the tail stream)."""
         B2, F, HW = 2 * bz, self.feat_dim, fh * fw
@@ -919,7 +1099,8 @@ class HandsLight(EngineSwitches, nn.Module):
         if self.use_grasp_loss and self.use_glb_feat_w_grasp:
             # sum-pool (model.py:196); only the grasp head reads it
             check(L.hands_sumpool_nhwc_f32(ptr(featg), ptr(feat_vec), bz, HW, F, F, stream), "sumpool")
-        ld = F + HMR_VEC
+        # HMR state rows [feat F | vectors 112] (hands_hmr_init_f32); the transformer head keeps the vectors only (`vo` = their column)
+        ld, vo = (HMR_VEC, 0) if self.tf_decoder else (F + HMR_VEC, F)
         state = buf("state", B2 * ld)
         if self.no_crops:
             # model.py:316-318 -> HandHMR.forward(features, use_pool=True) (hand_hmr.py:73-78): both heads read the average-pooled
@@ -943,14 +1124,15 @@ class HandsLight(EngineSwitches, nn.Module):
                 cat = feath            # pos_enc None / image-level: feature_conv reads the crop features as they are
             depth = self._depth_head(L, P, dev, stream, cat, B2, bz, fh, fw) if self.use_depth_loss else None
             # -- feature_conv (model.py:91-101, 313-314) -> HMR state rows ---------------------------
-            f1 = buf("fc1", B2 * HW * 1024)
-            self.engine.conv(L, P["fc0"], cat, B2, fh, fw, f1, True, stream)
-            f2 = buf("fc2", B2 * (fh - 2) * (fw - 2) * 512)
-            h2, w2 = self.engine.conv(L, P["fc2"], f1, B2, fh, fw, f2, True, stream)
-            f3 = buf("fc3", B2 * (h2 - 2) * (w2 - 2) * 256)
-            h3, w3 = self.engine.conv(L, P["fc4"], f2, B2, h2, w2, f3, True, stream, splitk_n=8)   # 3x3 output map: 72 tiles at bz=256, K=4608
-            assert h3 * w3 * 256 == P["fc7"].Cin
-            self.engine.conv(L, P["fc7"], f3, B2, 1, 1, state, True, stream, out_ps=ld, splitk=True)
+            if not self.tf_decoder:
+                f1 = buf("fc1", B2 * HW * 1024)
+                self.engine.conv(L, P["fc0"], cat, B2, fh, fw, f1, True, stream)
+                f2 = buf("fc2", B2 * (fh - 2) * (fw - 2) * 512)
+                h2, w2 = self.engine.conv(L, P["fc2"], f1, B2, fh, fw, f2, True, stream)
+                f3 = buf("fc3", B2 * (h2 - 2) * (w2 - 2) * 256)
+                h3, w3 = self.engine.conv(L, P["fc4"], f2, B2, h2, w2, f3, True, stream, splitk_n=8)   # 3x3 output map: 72 tiles at bz=256, K=4608
+                assert h3 * w3 * 256 == P["fc7"].Cin
+                self.engine.conv(L, P["fc7"], f3, B2, 1, 1, state, True, stream, out_ps=ld, splitk=True)
 
         # -- HandHMR x2 (hand_hmr.py:73-92, hmr_layer.py:67-86) ----------------------------------
         caminit4 = buf("caminit4", B2 * 4)
@@ -963,19 +1145,22 @@ class HandsLight(EngineSwitches, nn.Module):
             if hs is not main:
                 hs.wait_event(evh)
             sh = hs.cuda_stream
-            h512a, h512b = buf(f"h512a{side}", bz * 512), buf(f"h512b{side}", bz * 512)
-            x1, x2 = buf(f"x1024a{side}", bz * 1024), buf(f"x1024b{side}", bz * 1024)
-            so = side * bz * ld
-            self.engine.conv(L, hp["ci0"], state, bz, 1, 1, h512a, True, sh, in_ps=ld, x_off=so, splitk=True)
-            self.engine.conv(L, hp["ci2"], h512a, bz, 1, 1, h512b, True, sh, splitk=True)
-            self.engine.conv(L, hp["ci4"], h512b, bz, 1, 1, caminit4, False, sh, out_off=side * bz * 4)
-            check(L.hands_hmr_init_f32(ptr(state, so), ptr(caminit4, side * bz * 4), bz, ld, F, sh),
-                  "hmr_init")
-            for _ in range(3):
-                self.engine.conv(L, hp["r0"], state, bz, 1, 1, x1, True, sh, in_ps=ld, x_off=so, splitk=True)
-                self.engine.conv(L, hp["r3"], x1, bz, 1, 1, x2, True, sh, splitk=True)
-                self.engine.conv(L, hp["dec"], x2, bz, 1, 1, state, False, sh, res=state, out_ps=ld,
-                           res_ps=ld, out_off=so + F, res_off=so + F, splitk=True)
+            if self.tf_decoder:
+                self._tf_head(L, hp, dev, sh, side, bz, HW, cat, state, caminit4)
+            else:
+                h512a, h512b = buf(f"h512a{side}", bz * 512), buf(f"h512b{side}", bz * 512)
+                x1, x2 = buf(f"x1024a{side}", bz * 1024), buf(f"x1024b{side}", bz * 1024)
+                so = side * bz * ld
+                self.engine.conv(L, hp["ci0"], state, bz, 1, 1, h512a, True, sh, in_ps=ld, x_off=so, splitk=True)
+                self.engine.conv(L, hp["ci2"], h512a, bz, 1, 1, h512b, True, sh, splitk=True)
+                self.engine.conv(L, hp["ci4"], h512b, bz, 1, 1, caminit4, False, sh, out_off=side * bz * 4)
+                check(L.hands_hmr_init_f32(ptr(state, so), ptr(caminit4, side * bz * 4), bz, ld, F, sh),
+                      "hmr_init")
+                for _ in range(3):
+                    self.engine.conv(L, hp["r0"], state, bz, 1, 1, x1, True, sh, in_ps=ld, x_off=so, splitk=True)
+                    self.engine.conv(L, hp["r3"], x1, bz, 1, 1, x2, True, sh, splitk=True)
+                    self.engine.conv(L, hp["dec"], x2, bz, 1, 1, state, False, sh, res=state, out_ps=ld,
+                               res_ps=ld, out_off=so + F, res_off=so + F, splitk=True)
             if hs is not main:
                 ev = torch.cuda.Event()
                 ev.record(hs)
@@ -983,12 +1168,12 @@ class HandsLight(EngineSwitches, nn.Module):
         for ev in joins:
             main.wait_event(ev)
         rotmat = buf("rotmat", B2 * 144)
-        check(L.hands_rot6d_to_matrix_f32(ptr(state, F), ld, ptr(rotmat), B2, stream), "rot6d")
+        check(L.hands_rot6d_to_matrix_f32(ptr(state, vo), ld, ptr(rotmat), B2, stream), "rot6d")
         if self.rot_fix == 1:      # 'pcl' (model.py:330-334): in place on the heads' output -- the flip swap and the grasp head see it
             check(L.hands_rot_leftmul_f32(ptr(rotmat), ptr(rot_in), B2, stream), "rot_leftmul")
         st = state[: B2 * ld].view(B2, ld)
-        shape = st[:, F + 96:F + 106].contiguous()
-        cam = st[:, F + 108:F + 111].contiguous()
+        shape = st[:, vo + 96:vo + 106].contiguous()
+        cam = st[:, vo + 108:vo + 111].contiguous()
         caminit = caminit4[: B2 * 4].view(B2, 4)[:, :3].contiguous()
 
         # -- is_flipped swap (model.py:341-368), per sample on device ----------------------------
@@ -1037,7 +1222,7 @@ class HandsLight(EngineSwitches, nn.Module):
         Fg = F if self.use_glb_feat_w_grasp else 0
         gld = P["g0"].Cin
         gin = buf("grasp_in", B2 * gld)
-        check(L.hands_grasp_input_f32(ptr(state, F + 96), ld, ptr(rotmat), ptr(feat_vec), ptr(gin), B2, bz,
+        check(L.hands_grasp_input_f32(ptr(state, vo + 96), ld, ptr(rotmat), ptr(feat_vec), ptr(gin), B2, bz,
                                       Fg, gld, stream), "grasp_input")
         g1, g2, g3 = buf("g1", B2 * 1024), buf("g2", B2 * 512), buf("g3", B2 * 128)
         g4 = torch.empty(B2, 12, device=dev)

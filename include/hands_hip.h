@@ -462,6 +462,33 @@ int hands_vit_tokens_f32(const float* patch, const float* class_token, const flo
 int hands_vit_tail_f32(const float* x, const float* gamma, const float* beta, float* out, int B, int grid, int C, float eps,
                        hands_stream_t stream);
 
+/* ---- transformer head of hands_light (HandsLight(tf_decoder=True): hmr_layer.py:17-42, 67-86, hand_hmr.py:19-31, 57-62,
+ * hands_light/transformer.py with no_norm=True).  Its Linear layers (in_proj, out_proj, linear1 / linear2, feat_mlp,
+ * cam_init_precursor, the decoders) run on hands_conv2d_nhwc_f32 with the bias / ReLU / residual epilogue. ---- */
+
+/* Single-head attention at a wide head dimension: out[b] = softmax(scale * Q[b] K[b]^T) V[b], Q (Tq, D), K and V (Tk, D),
+ * out (Tq, D); 1 <= Tq, Tk <= 128, D a multiple of 64 (1024 in the head).  Every operand has its own row stride ld* (floats,
+ * >= D, a multiple of 4) and batch stride (floats, a multiple of 4), so the packed (B, T, 3 D) output of in_proj and a
+ * (B, Tk, 2 D) [k | v] buffer are read in place; all four pointers 16-byte aligned.  D streams through LDS in 64-float chunks
+ * on v_mfma_f32_16x16x4_f32 while the Tq x Tk scores stay in registers; the D-sum of a score is blocked (64 products per block,
+ * blocks added in order).  Keys >= Tk carry exactly zero weight; only rows < Tq and columns < D of `out` are written.  The
+ * summation order depends on (Tq, Tk, D) only: a batch element's result does not depend on B.  Anything outside this contract
+ * (and B > 65535) returns HANDS_EINVAL without a launch. */
+int hands_wide_attention_f32(const float* q, long long q_batch_stride, int ldq, const float* k, long long k_batch_stride, int ldk,
+                             const float* v, long long v_batch_stride, int ldv, float* out, long long out_batch_stride, int ldo,
+                             int B, int Tq, int Tk, int D, float scale, hands_stream_t stream);
+
+/* out[b,t,:] = relu(vec[b*ldvec + col(t)] * w + bias): nn.Linear(1, C) + ReLU on every scalar of the (B, T) vector buffer
+ * (`vector_mlp`, hmr_layer.py:72-73).  col(t) = t for t < split and t + gap from there on: the HMR state row
+ * [pose6d 96 | shape 10 | 0 0 | cam 3 | 0] is read in place with split = 106, gap = 2; a dense (B, T) buffer with split = T,
+ * gap = 0.  w, bias (C); out (B, T, C); C % 4 == 0; ldvec covers the last token's column. */
+int hands_vector_tokens_f32(const float* vec, int ldvec, int split, int gap, const float* w, const float* bias, float* out, int B,
+                            int T, int C, hands_stream_t stream);
+
+/* out[b,c] = (sum_t x[b,t,c]) / N (torch.mean over the tokens, hmr_layer.py:78), the sum in hands_token_sum_f32's fixed order.
+ * C % 64 == 0. */
+int hands_token_mean_f32(const float* x, float* out, int B, int N, int C, hands_stream_t stream);
+
 /* one query token per sample against T context tokens: q (B, heads*64), kv rows [k | v] (B*T,
  * 2*heads*64) -> out (B, heads*64); dots = (q.k)*scale (pose_transformer.py:113-123). */
 int hands_cross_attention_1q_f32(const float* q, const float* kv, float* out, int B, int T, int heads,
