@@ -53,6 +53,24 @@ class EvalOut(C.Structure):
         "mpjpe_ra_h", "mpjpe_pa_ra_r", "mpjpe_pa_ra_l", "mpjpe_pa_ra_h", "mrrpe_rl", "pix_err_r", "pix_err_l")]
 
 
+class LossIn(C.Structure):
+    """hands_loss_in (include/hands_hip.h): the first LOSS_N_MANDATORY pointers are mandatory, the rest come in groups."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "pred_pose_r", "pred_pose_l", "pred_beta_r", "pred_beta_l", "pred_j3d_r", "pred_j3d_l", "pred_j2d_r", "pred_j2d_l",
+        "pred_cam_wp_r", "pred_cam_wp_l", "pred_cam_wp_init_r", "pred_cam_wp_init_l",
+        "gt_pose_r", "gt_pose_l", "gt_beta_r", "gt_beta_l", "gt_j3d_r", "gt_j3d_l", "gt_j2d_r", "gt_j2d_l",
+        "gt_cam_wp_r", "gt_cam_wp_l", "right_valid", "left_valid", "joints_valid_r", "joints_valid_l",
+        "is_cam_loss", "is_j2d_loss", "is_j3d_loss", "is_pose_loss", "is_beta_loss",
+        "pred_grasp_r", "pred_grasp_l", "gt_grasp_r", "gt_grasp_l", "grasp_valid_r", "grasp_valid_l", "is_grasp_loss",
+        "pred_mask_r", "pred_mask_l", "gt_mask_r", "gt_mask_l", "render_valid_r", "render_valid_l", "is_mask_loss",
+        "pred_depth_r", "pred_depth_l", "gt_depth_r", "gt_depth_l", "is_depth_loss",
+        "pred_center_r", "pred_center_l", "gt_center_r", "gt_center_l",
+        "pred_corner_r", "pred_corner_l", "gt_corner_r", "gt_corner_l")]
+
+
+LOSS_NKEYS, LOSS_N_MANDATORY = 21, 31     # HANDS_LOSS_NKEYS, HANDS_LOSS_N_MANDATORY
+
+
 class ShadeMesh(C.Structure):
     """hands_shade_mesh (include/hands_hip.h): one mesh of a shaded picture."""
     _fields_ = [("workspace", C.c_void_p), ("faces", C.c_void_p), ("valid", C.c_void_p), ("n_verts", C.c_int32),
@@ -140,6 +158,7 @@ SIGNATURES = {
     "hands_flash_attention_f32": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     "hands_ceiling_hbm_read_f32": [_P, C.c_longlong, _P, _P],
     "hands_eval_metrics_f32": [C.POINTER(EvalIn), C.POINTER(EvalOut), _I, _P],
+    "hands_loss_light_f32": [C.POINTER(LossIn), _I, _I, _I, _P, _P, _P, _P, _P],
     "hands_mano_pose_aa_f32": [C.POINTER(ManoConsts), _P, _P, _I, _P, _I, _P, _P, _I, _P],
     "hands_gt_targets_f32": [_P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _P],
     "hands_unnormalize_kp2d_f32": [_P, _P, C.c_longlong, _F, _P],
@@ -160,7 +179,8 @@ SIGNATURES = {
 }
 EXTRA_SYMBOLS = ("hands_abi_version", "hands_error_string", "hands_conv2d_workspace_floats", "hands_pack_conv3x3_winograd_floats", "hands_conv3x3_winograd_executed_macs",
                  "hands_pack_conv3x3_winograd4_floats", "hands_conv3x3_winograd4_executed_macs",
-                 "hands_conv2d_streamk_workspace_bytes", "hands_stream_is_capturing", "hands_csrc_sha16", "hands_ceiling_mfma_f32", "hands_mesh_workspace_floats")
+                 "hands_conv2d_streamk_workspace_bytes", "hands_stream_is_capturing", "hands_csrc_sha16", "hands_ceiling_mfma_f32", "hands_mesh_workspace_floats",
+                 "hands_loss_workspace_bytes")
 
 ABI_VERSION = 5      # HANDS_ABI_VERSION of include/hands_hip.h this wrapper was written against
 _lib = None
@@ -206,6 +226,8 @@ def lib():
     h.hands_ceiling_mfma_f32.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p]
     h.hands_mesh_workspace_floats.restype = C.c_longlong
     h.hands_mesh_workspace_floats.argtypes = [C.c_int, C.c_int]
+    h.hands_loss_workspace_bytes.restype = C.c_longlong
+    h.hands_loss_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     h.hands_error_string.restype = C.c_char_p
     h.hands_error_string.argtypes = [C.c_int]
     _lib = h

@@ -2,10 +2,12 @@
 
 The reference's ``HandsWrapper(GenericWrapper(AbstractPL(LightningModule)))``
 (src/models/hands_light/wrapper.py:11-25, src/models/generic/wrapper.py:27-75) is a training
-harness; only ``inference`` / ``inference_pose`` sit on the forward path and that is what this
+harness; ``inference`` / ``inference_pose`` and the validation call ``forward(..., "test")`` are what this
 class reproduces: run the model, merge ``inputs.*`` + ``pred.*`` + ``meta_info.*`` into one strict
-dict and move every tensor to the CPU (generic/wrapper.py:68-75).  Like the reference it does not
-switch the module to eval mode; the HIP path has no train-mode behaviour anyway.
+dict and move every tensor to the CPU (generic/wrapper.py:68-75); in ``forward``, GT preprocessing, the
+metrics and -- on request -- the loss dict ``loss__val`` is averaged from (hands_amd/losses.py), all on
+device.  Like the reference it does not switch the module to eval mode; the HIP path has no train-mode
+behaviour anyway: gradients, optimisers and ``mode="train"`` stay out of scope.
 """
 from __future__ import annotations
 
@@ -89,17 +91,42 @@ class HandsWrapper(nn.Module):
                                            torch.cuda.current_stream(t.device).cuda_stream), "unnormalize_kp2d")
         return out
 
-    def forward(self, inputs, targets=None, meta_info=None, mode="test"):
+    def _mask_renderer(self):
+        """The soft-silhouette renderer of the mask loss, built on first use from the model's MANO face lists."""
+        r = self.__dict__.get("_mask_renderer_obj")
+        if r is None:
+            from .render import MANORenderer
+            r = MANORenderer({"img_res": int(getattr(self.model, "img_res", 224))},
+                             faces=(self.model.mano_r.faces, self.model.mano_l.faces))
+            self.__dict__["_mask_renderer_obj"] = r
+        return r
+
+    def forward(self, inputs, targets=None, meta_info=None, mode="test", compute_loss=False, loss_args=None):
         """GenericWrapper.forward without the training parts (src/models/generic/wrapper.py:77-164):
-        GT preprocessing -> model -> 2-D de-normalisation -> metrics (``test``) / merged dict (``vis``,
-        ``extract``).  Losses are training-only and out of scope: the loss dict is returned empty."""
+        GT preprocessing -> model -> [loss dict] -> 2-D de-normalisation -> metrics (``test``) / merged dict
+        (``vis``, ``extract``).
+
+        By default the loss dict is returned empty.  With ``compute_loss=True`` the reference's
+        ``compute_loss_light(pred, targets, meta_info, loss_args or self.args)`` is evaluated on device where the
+        reference calls it (generic/wrapper.py:97-115) and ``test`` returns the weighted 0-dim values plus their sum
+        under ``'loss'``; forward evaluation only -- ``mode="train"`` raises.  If the loss args switch
+        ``use_render_seg_loss`` on and the model gave no ``render.r``, ``MANORenderer.render_masks`` fills
+        ``render.{r,l}`` into the predictions first."""
         if mode not in ("test", "extract", "vis"):
-            raise NotImplementedError("hands_amd.HandsWrapper: the training mode (losses, optimiser) is out of scope")
+            raise NotImplementedError("hands_amd.HandsWrapper: the training mode (gradients, optimiser) is out of scope")
         inputs, targets, meta_info = xdict(inputs), xdict(targets or {}), xdict(meta_info)
         targets = self.process_data(targets, meta_info)
         meta_info.overwrite("mano.faces.r", self.model.mano_r.faces)      # generic/wrapper.py:93-94
         meta_info.overwrite("mano.faces.l", self.model.mano_l.faces)
         pred = self.model(inputs, meta_info)
+        loss_dict = {}
+        if compute_loss:                                                   # generic/wrapper.py:97-115
+            from .losses import compute_loss_light, mul_loss_dict, total_loss
+            largs = loss_args if loss_args is not None else self.args
+            lget = largs.get if hasattr(largs, "get") else (lambda k, d=None: getattr(largs, k, d))
+            if lget("use_render_seg_loss", False) and "render.r" not in pred:
+                pred.merge(self._mask_renderer().render_masks(pred, meta_info))
+            loss_dict = dict(total_loss(mul_loss_dict(compute_loss_light(pred, targets, meta_info, largs))))
         for key in list(pred.keys()):                                      # generic/wrapper.py:118-134
             if "2d.norm" in key:
                 assert key in targets.keys(), f"Do not have key {key}"
@@ -118,7 +145,7 @@ class HandsWrapper(nn.Module):
         out_dict.merge({"metric." + k: v for k, v in metrics_all.items()})
         if mode == "extract":
             return merged()
-        return out_dict, {}
+        return out_dict, loss_dict
 
 
 class HaMeRWrapper(HandsWrapper):

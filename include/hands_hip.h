@@ -577,6 +577,62 @@ typedef struct hands_eval_out {
 int hands_eval_metrics_f32(const hands_eval_in* in, const hands_eval_out* out, int B,
                            hands_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The validation loss dict on device, forward only (csrc/loss.hip): compute_loss_light of
+ * src/callbacks/loss/loss_arctic_sf.py:20-206 (vector_loss / joints_loss / grasp_loss / render_loss of
+ * src/utils/loss_modules.py:97-152) with the weighting and the total of src/models/generic/wrapper.py:19-23,100-115.
+ * Two launches on `stream` whatever terms are present, no host synchronisation, no atomics: the outputs are
+ * bit-reproducible from run to run.
+ *
+ * Every value is the mean over ALL B*D elements of (difference -> square or abs -> x validity -> x is_*_loss), elements in
+ * fp32, accumulation in fp64.  A vector_loss term (cam_t, pose, beta, transl, center, corner) whose validity vector sums to
+ * zero is exactly 0, NaNs included; otherwise a NaN of an invalid sample propagates, as in the reference.
+ *
+ * Shapes (fp32 unless stated; flags and validities are per sample (B) except joints_valid (B,21)):
+ *   pred_pose (B,16,3,3) rotation matrices against gt_pose (B,48) axis-angle; beta (B,10); j3d (B,21,3) camera-space joints
+ *   (compared root-relative); j2d (B,21,2) normalised; cam_wp / cam_wp_init (B,3); grasp logits (B,9) against int64 labels
+ *   (B) -- ASSUMED in [0, 9), NOT checked on the device; mask (B,S_mask,S_mask) and depth (B,S_depth,S_depth), contiguous;
+ *   center (B,2), corner (B,8).
+ * The first HANDS_LOSS_N_MANDATORY pointers are mandatory.  Each optional group (grasp, mask, depth, center+corner) is all
+ * there or all NULL; a NULL group's keys are skipped (outputs 0, not part of the total).
+ *
+ * Output order (HANDS_LOSS_NKEYS = 21) and weights, as the reference's dict: cam_t/r 1, cam_t/l 1, kp2d/r 5, kp3d/r 5,
+ * pose/r 10, beta/r 0.001, kp2d/l 5, kp3d/l 5, pose/l 10, transl/l 1, beta/l 0.001, grasp/{r,l} 0.1, mask/{r,l} 10,
+ * depth/{r,l} 1, center/{r,l} 1, corner/{r,l} 1.  out_weighted21[k] = out_unweighted21[k] * weight[k] (fp32), out_total[0] =
+ * their sum over the present keys in that order (fp32).
+ *
+ * workspace: hands_loss_workspace_bytes(B, S_mask, S_depth) bytes (0 for a bad shape), 8-byte aligned, caller-owned, every
+ * byte the second launch reads is written by the first (no zero-fill needed).  S of an absent group is ignored.
+ * HANDS_EINVAL (nothing launched): a NULL mandatory pointer / workspace / output, B <= 0, a half-given group, S outside
+ * [1, 32768] for a present group.
+ * --------------------------------------------------------------------------------------------- */
+#define HANDS_LOSS_NKEYS 21
+#define HANDS_LOSS_N_MANDATORY 31
+typedef struct hands_loss_in {
+  /* mandatory (31) */
+  const float *pred_pose_r, *pred_pose_l, *pred_beta_r, *pred_beta_l, *pred_j3d_r, *pred_j3d_l, *pred_j2d_r, *pred_j2d_l;
+  const float *pred_cam_wp_r, *pred_cam_wp_l, *pred_cam_wp_init_r, *pred_cam_wp_init_l;
+  const float *gt_pose_r, *gt_pose_l, *gt_beta_r, *gt_beta_l, *gt_j3d_r, *gt_j3d_l, *gt_j2d_r, *gt_j2d_l;
+  const float *gt_cam_wp_r, *gt_cam_wp_l;
+  const float *right_valid, *left_valid, *joints_valid_r, *joints_valid_l;
+  const float *is_cam_loss, *is_j2d_loss, *is_j3d_loss, *is_pose_loss, *is_beta_loss;
+  /* use_grasp_loss */
+  const float *pred_grasp_r, *pred_grasp_l;
+  const long long *gt_grasp_r, *gt_grasp_l;
+  const float *grasp_valid_r, *grasp_valid_l, *is_grasp_loss;
+  /* use_render_seg_loss */
+  const float *pred_mask_r, *pred_mask_l, *gt_mask_r, *gt_mask_l, *render_valid_r, *render_valid_l, *is_mask_loss;
+  /* use_depth_loss */
+  const float *pred_depth_r, *pred_depth_l, *gt_depth_r, *gt_depth_l, *is_depth_loss;
+  /* regress_center_corner */
+  const float *pred_center_r, *pred_center_l, *gt_center_r, *gt_center_l;
+  const float *pred_corner_r, *pred_corner_l, *gt_corner_r, *gt_corner_l;
+} hands_loss_in;
+
+long long hands_loss_workspace_bytes(int B, int S_mask, int S_depth);
+int hands_loss_light_f32(const hands_loss_in* in, int B, int S_mask, int S_depth, void* workspace,
+                         float* out_unweighted21, float* out_weighted21, float* out_total, hands_stream_t stream);
+
 /* GT preprocessing of the wrapper's test mode (src/callbacks/process/process_arctic.py:4-75):
  *   hands_mano_pose_aa_f32   = hands_mano_pose_f32 for AXIS-ANGLE input (B,48) (GT MANO parameters);
  *   hands_gt_targets_f32     : Tr0 = mean_j(j3d_full - joints); v3d_cam = verts + Tr0;
