@@ -30,6 +30,23 @@ __device__ __forceinline__ float exp_nonpos(float x) {
   return ldexpf(__builtin_amdgcn_exp2f(f), (int)n);
 }
 
+// Source tap of bilinear interpolation, align_corners=False (ATen's area_pixel_compute_source_index): destination index dst of a
+// resize n_in -> n_out reads src = max(0, (dst + 0.5) * n_in / n_out - 0.5) -> i0 = floor(src), i1 = min(i0 + 1, n_in - 1), weight
+// `l` of i1.  The coordinate is formed in fp64 and rounded once, as the weight: in fp32 a ratio that is not a dyadic fraction
+// (200 -> 96: 2.08333...) loses |src| * 2^-24 of the weight, 4e-5 of a randn image's pixel at column 160 -- tests/
+// test_gpu_kernel_edges.py holds every ratio to 2e-6.  Where ratio and coordinate are exact in fp32 (the models' 2x and
+// 224 -> 256) both forms give the same bits.
+struct LerpTap { int i0, i1; float l; };
+__device__ __forceinline__ LerpTap lerp_tap(int dst, double scale, int n_in) {
+  double s = ((double)dst + 0.5) * scale - 0.5;
+  s = s < 0.0 ? 0.0 : s;
+  LerpTap t;
+  t.i0 = (int)s;
+  t.i1 = t.i0 + (t.i0 < n_in - 1 ? 1 : 0);
+  t.l = (float)(s - (double)t.i0);
+  return t;
+}
+
 // 16 bytes at p when `real`, zeros otherwise (padded tokens: nothing is read past the tensor)
 __device__ __forceinline__ float4 ld4_or_zero(bool real, const float* p) {
   float4 r = make_float4(0.f, 0.f, 0.f, 0.f);

@@ -433,7 +433,7 @@ __global__ void axis_angle_to_matrix_kernel(const float* __restrict__ aa, float*
 extern "C" {
 
 int hands_nchw3_to_nhwc4_f32(const float* in, float* out, int B, int H, int W, hands_stream_t stream) {
-  if (!in || !out || B <= 0) return HANDS_EINVAL;
+  if (!in || !out || B <= 0 || H <= 0 || W <= 0) return HANDS_EINVAL;
   const long long n = (long long)B * H * W;
   hipLaunchKernelGGL(nchw3_to_nhwc4_kernel, dim3(hands_grid_1d(n, 256)), dim3(256), 0,
                      (hipStream_t)stream, in, (float4*)out, n, H * W);
@@ -442,7 +442,7 @@ int hands_nchw3_to_nhwc4_f32(const float* in, float* out, int B, int H, int W, h
 
 int hands_maxpool3x3s2_nhwc_f32(const float* in, float* out, int B, int H, int W, int C,
                                 hands_stream_t stream) {
-  if (!in || !out || B <= 0 || C % 4) return HANDS_EINVAL;
+  if (!in || !out || B <= 0 || H <= 0 || W <= 0 || C % 4) return HANDS_EINVAL;
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   const long long n = (long long)B * Ho * Wo * (C / 4);
   hipLaunchKernelGGL(maxpool3x3s2_kernel, dim3(hands_grid_1d(n, 256, 256 * 16)), dim3(256), 0,
@@ -452,7 +452,7 @@ int hands_maxpool3x3s2_nhwc_f32(const float* in, float* out, int B, int H, int W
 
 int hands_sumpool_nhwc_f32(const float* feat, float* out, int B, int HW, int C, int out_stride,
                            hands_stream_t stream) {
-  if (!feat || !out || B <= 0 || C % 4 || out_stride % 4) return HANDS_EINVAL;
+  if (!feat || !out || B <= 0 || HW <= 0 || C % 4 || out_stride % 4) return HANDS_EINVAL;
   hipLaunchKernelGGL(sumpool_kernel, dim3(hands_grid_1d((long long)B * C / 4, 64)), dim3(64), 0,
                      (hipStream_t)stream, (const float4*)feat, out, B, HW, C / 4, out_stride);
   HANDS_LAUNCH_CHECK();

@@ -21,18 +21,16 @@ __device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(
 __global__ void upsample_bilinear_add_kernel(const float4* __restrict__ x, const float4* __restrict__ y,
                                              float4* __restrict__ out, int B, int h, int w, int H, int W, int C4) {
   const long long total = (long long)B * H * W * C4;
-  const float sh = (float)h / (float)H, sw = (float)w / (float)W;
+  const double sh = (double)h / (double)H, sw = (double)w / (double)W;
   GRID_STRIDE(i, total) {
     const int c = (int)(i % C4);
     long long t = i / C4;
     const int xo = (int)(t % W); t /= W;
     const int yo = (int)(t % H);
     const int b = (int)(t / H);
-    float sy = ((float)yo + 0.5f) * sh - 0.5f; sy = sy < 0.f ? 0.f : sy;
-    float sx = ((float)xo + 0.5f) * sw - 0.5f; sx = sx < 0.f ? 0.f : sx;
-    const int y0 = (int)sy, x0 = (int)sx;
-    const int y1 = y0 + (y0 < h - 1 ? 1 : 0), x1 = x0 + (x0 < w - 1 ? 1 : 0);
-    const float ly = sy - (float)y0, lx = sx - (float)x0, hy = 1.f - ly, hx = 1.f - lx;
+    const LerpTap ty = lerp_tap(yo, sh, h), tx = lerp_tap(xo, sw, w);
+    const int y0 = ty.i0, y1 = ty.i1, x0 = tx.i0, x1 = tx.i1;
+    const float ly = ty.l, lx = tx.l, hy = 1.f - ly, hx = 1.f - lx;
     const float4* base = x + (long long)b * h * w * C4 + c;
     const float4 p00 = base[(long long)(y0 * w + x0) * C4], p01 = base[(long long)(y0 * w + x1) * C4];
     const float4 p10 = base[(long long)(y1 * w + x0) * C4], p11 = base[(long long)(y1 * w + x1) * C4];
@@ -403,7 +401,7 @@ extern "C" {
 
 int hands_upsample_bilinear_add_f32(const float* x, const float* y, float* out, int B, int h, int w, int H, int W,
                                     int C, hands_stream_t stream) {
-  if (!x || !y || !out || B <= 0 || C % 4) return HANDS_EINVAL;
+  if (!x || !y || !out || B <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0 || C % 4) return HANDS_EINVAL;
   hipLaunchKernelGGL(upsample_bilinear_add_kernel, dim3(hands_grid_1d((long long)B * H * W * C / 4, 256)), dim3(256), 0,
                      S(stream), (const float4*)x, (const float4*)y, (float4*)out, B, h, w, H, W, C / 4);
   HANDS_LAUNCH_CHECK();
@@ -463,7 +461,7 @@ int hands_bn_leaky_f32(const float* x, const float* scale, const float* shift, f
 
 int hands_upsample_nearest2x_add_f32(const float* low, const float* up1, float* out, int B, int h, int w, int C,
                                      hands_stream_t stream) {
-  if (!low || !up1 || !out || B <= 0 || C % 4) return HANDS_EINVAL;
+  if (!low || !up1 || !out || B <= 0 || h <= 0 || w <= 0 || C % 4) return HANDS_EINVAL;
   hipLaunchKernelGGL(upsample_nearest2x_add_kernel, dim3(hands_grid_1d((long long)B * 4 * h * w * C / 4, 256)), dim3(256),
                      0, S(stream), (const float4*)low, (const float4*)up1, (float4*)out, B, h, w, C / 4);
   HANDS_LAUNCH_CHECK();
@@ -471,7 +469,7 @@ int hands_upsample_nearest2x_add_f32(const float* low, const float* up1, float* 
 
 int hands_spatial_softmax_f32(const float* latents, int ld_in, const float* betas, float* heatmaps, int ld_out, int B,
                               int N, int J, hands_stream_t stream) {
-  if (!latents || !betas || !heatmaps || B <= 0 || J <= 0 || ld_in < J || ld_out < J) return HANDS_EINVAL;
+  if (!latents || !betas || !heatmaps || B <= 0 || N <= 0 || J <= 0 || ld_in < J || ld_out < J) return HANDS_EINVAL;
   hipLaunchKernelGGL(spatial_softmax_kernel, dim3(ld_out, B), dim3(256), 0, S(stream), latents, ld_in, betas, heatmaps,
                      ld_out, N, J);
   HANDS_LAUNCH_CHECK();
@@ -480,7 +478,8 @@ int hands_spatial_softmax_f32(const float* latents, int ld_in, const float* beta
 int hands_flash_attention_f32(const float* q, const float* k, const float* v, const float* q2, const float* k2sum,
                               const float* resid, float* out, int B, int N, int heads, int head_dim, float scale,
                               hands_stream_t stream) {
-  if (!q || !k || !v || !out || B <= 0 || heads <= 0 || head_dim != 64 || N % 128 || (q2 && !k2sum)) return HANDS_EINVAL;
+  if (!q || !k || !v || !out || B <= 0 || heads <= 0 || head_dim != 64 || N <= 0 || N % 128 || (q2 && !k2sum))
+    return HANDS_EINVAL;
   const long long nwg = (long long)B * heads * (N / 128);
   if (nwg > 0x7fffffffLL) return HANDS_EINVAL;
   // scale a power of two (head_dim 64 -> 0.125): folded into q exactly; any other value is applied after the product

@@ -16,19 +16,16 @@ namespace {
 __global__ void resize_crop_kernel(const float* __restrict__ in, float4* __restrict__ out, int B, int Hin,
                                    int Win, int S, int col0, int Wc) {
   const long long total = (long long)B * S * Wc;
-  const float sh = (float)Hin / (float)S, sw = (float)Win / (float)S;
+  const double sh = (double)Hin / (double)S, sw = (double)Win / (double)S;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
        i += (long long)gridDim.x * blockDim.x) {
     const int xo = (int)(i % Wc);
     long long t = i / Wc;
     const int yo = (int)(t % S);
     const int b = (int)(t / S);
-    // area_pixel_compute_source_index: max(0, (dst + 0.5) * scale - 0.5)
-    float sy = ((float)yo + 0.5f) * sh - 0.5f; sy = sy < 0.f ? 0.f : sy;
-    float sx = ((float)(xo + col0) + 0.5f) * sw - 0.5f; sx = sx < 0.f ? 0.f : sx;
-    const int y0 = (int)sy, x0 = (int)sx;
-    const int y1 = y0 + (y0 < Hin - 1 ? 1 : 0), x1 = x0 + (x0 < Win - 1 ? 1 : 0);
-    const float ly = sy - (float)y0, lx = sx - (float)x0;
+    const LerpTap ty = lerp_tap(yo, sh, Hin), tx = lerp_tap(xo + col0, sw, Win);
+    const int y0 = ty.i0, y1 = ty.i1, x0 = tx.i0, x1 = tx.i1;
+    const float ly = ty.l, lx = tx.l;
     const float hy = 1.f - ly, hx = 1.f - lx;
     float r[3];
 #pragma unroll
@@ -390,7 +387,7 @@ extern "C" {
 
 int hands_resize_crop_nchw3_to_nhwc4_f32(const float* in, float* out, int B, int Hin, int Win, int S, int col0,
                                          int Wc, hands_stream_t stream) {
-  if (!in || !out || B <= 0 || S <= 0 || col0 < 0 || col0 + Wc > S) return HANDS_EINVAL;
+  if (!in || !out || B <= 0 || Hin <= 0 || Win <= 0 || S <= 0 || col0 < 0 || Wc <= 0 || col0 + Wc > S) return HANDS_EINVAL;
   hipLaunchKernelGGL(resize_crop_kernel, dim3(hands_grid_1d((long long)B * S * Wc, 256)), dim3(256), 0,
                      (hipStream_t)stream, in, (float4*)out, B, Hin, Win, S, col0, Wc);
   HANDS_LAUNCH_CHECK();

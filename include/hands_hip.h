@@ -248,14 +248,15 @@ int hands_stem_conv_maxpool_nchw_f32(const float* x_nchw, const float* w_planar,
                                      int B, int H, int W, int act, hands_stream_t stream);
 
 /* NCHW (B,3,H,W) image batch -> NHWC with C padded to 4 (4th channel = 0).
- * Replaces the implicit layout of inputs["img"|"r_img"|"l_img"] (model.py:188,238-239). */
+ * Replaces the implicit layout of inputs["img"|"r_img"|"l_img"] (model.py:188,238-239).  B, H, W >= 1, else HANDS_EINVAL. */
 int hands_nchw3_to_nhwc4_f32(const float* in, float* out, int B, int H, int W, hands_stream_t stream);
 
-/* MaxPool2d(kernel 3, stride 2, padding 1) on NHWC.  resnet.py:268. C % 4 == 0. */
+/* MaxPool2d(kernel 3, stride 2, padding 1) on NHWC.  resnet.py:268. C % 4 == 0; B, H, W >= 1, else HANDS_EINVAL. */
 int hands_maxpool3x3s2_nhwc_f32(const float* in, float* out, int B, int H, int W, int C,
                                 hands_stream_t stream);
 
-/* feat_vec[b, c] = sum_p feat[b, p, c]  (a SUM over the 7x7 map, not a mean).  model.py:196. */
+/* feat_vec[b, c] = sum_p feat[b, p, c]  (a SUM over the 7x7 map, not a mean).  model.py:196.
+ * C % 4 == 0, out_stride % 4 == 0; B, HW >= 1, else HANDS_EINVAL. */
 int hands_sumpool_nhwc_f32(const float* feat, float* out, int B, int HW, int C, int out_stride,
                            hands_stream_t stream);
 
@@ -418,7 +419,8 @@ int hands_mano_heads_f32(const hands_mano_side* sides, int n_sides, const float*
  * --------------------------------------------------------------------------------------------- */
 
 /* F.interpolate(bilinear, align_corners=False) (Hin,Win)->(S,S) of an NCHW (B,3,..) batch, keep
- * columns [col0, col0+Wc), write NHWC4 (B,S,Wc,4).  hamer_light/model.py:82-100. */
+ * columns [col0, col0+Wc), write NHWC4 (B,S,Wc,4).  hamer_light/model.py:82-100.
+ * B, Hin, Win, S, Wc >= 1 and 0 <= col0 <= S - Wc, else HANDS_EINVAL. */
 int hands_resize_crop_nchw3_to_nhwc4_f32(const float* in, float* out, int B, int Hin, int Win, int S,
                                          int col0, int Wc, hands_stream_t stream);
 
@@ -504,7 +506,8 @@ int hands_rot6d_to_matrix_cols_f32(const float* pose6d, int ld6, float* rotmat, 
  * (HANDS_ACT_LEAKY_RELU epilogue); all tensors NHWC, C % 4 == 0.
  * --------------------------------------------------------------------------------------------- */
 
-/* out = F.interpolate(x (B,h,w,C) -> (H,W), bilinear, align_corners=False) + y.  backbone.py:40-42. */
+/* out = F.interpolate(x (B,h,w,C) -> (H,W), bilinear, align_corners=False) + y.  backbone.py:40-42.
+ * C % 4 == 0; B, h, w, H, W >= 1, else HANDS_EINVAL. */
 int hands_upsample_bilinear_add_f32(const float* x, const float* y, float* out, int B, int h, int w,
                                     int H, int W, int C, hands_stream_t stream);
 
@@ -538,19 +541,20 @@ int hands_token_sum_f32(const float* x, float* out, int B, int N, int C, hands_s
 int hands_bn_leaky_f32(const float* x, const float* scale, const float* shift, float* out,
                        long long npix, int C, hands_stream_t stream);
 
-/* out = up1 + nearest_upsample_2x(low (B,h,w,C))   (hand_head.py:228-230). */
+/* out = up1 + nearest_upsample_2x(low (B,h,w,C))   (hand_head.py:228-230).  C % 4 == 0; B, h, w >= 1, else HANDS_EINVAL. */
 int hands_upsample_nearest2x_add_f32(const float* low, const float* up1, float* out, int B, int h,
                                      int w, int C, hands_stream_t stream);
 
 /* heatmaps[b,t,j] = softmax_t(latents[b,t,j] * betas[j]) for j < J, 0 for J <= j < ld_out
- * (hand_head.py:62-67).  Row strides ld_in / ld_out. */
+ * (hand_head.py:62-67).  Row strides ld_in / ld_out (>= J).  B, N, J >= 1, else HANDS_EINVAL. */
 int hands_spatial_softmax_f32(const float* latents, int ld_in, const float* betas, float* heatmaps,
                               int ld_out, int B, int N, int J, hands_stream_t stream);
 
 /* softmax((q k^T) * scale) v per (batch, head) with online softmax on fp32 MFMA; q,k,v,out (B*N,
  * heads*64).  Optional FIT gate: output rows scaled by sigmoid((q2 . k2sum[b]) * scale), k2sum (B,
  * heads*64) = sum over the tokens of k2; optional residual added to the output.
- * transformer.py:71-98,146-153.  N % 128 == 0, head_dim == 64. */
+ * transformer.py:71-98,146-153.  N a positive multiple of 128, head_dim == 64, k2sum given whenever q2 is; anything else
+ * (N = 0 included) returns HANDS_EINVAL without a launch. */
 int hands_flash_attention_f32(const float* q, const float* k, const float* v, const float* q2,
                               const float* k2sum, const float* resid, float* out, int B, int N,
                               int heads, int head_dim, float scale, hands_stream_t stream);
