@@ -2,6 +2,11 @@
 // root-aligned MPJPE, Procrustes-aligned MPJPE (3x3 SVD per hand), hand-to-hand MRRPE, 2-D pixel error.
 // Reference: src/utils/eval_modules.py:97-134,136-219,320-343,386-428; common/metrics.py:23-55;
 // common/torch_utils.py:14-19 (nanmean).  One thread per sample; the work is ~2 kFLOP per hand.
+// Rank-deficient Procrustes: the rotation is V diag(1,1,det V) U^T with U an orthonormal frame whatever the rank of the
+// cross-covariance K.  Rank 2 (planar joints): U_2 = U_0 x U_1.  Rank 1 (the predicted or the ground-truth joints on a line):
+// U_1 is completed from the unit axis least aligned with U_0; the error does not depend on the completion and equals the one
+// of the reference's LAPACK SVD.  K = 0: a constant prediction gives NaN (scale = 0 / 0, as the reference), a constant ground
+// truth gives 0.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "hands_hip.h"
@@ -84,11 +89,34 @@ __device__ float mpjpe_pa(const float* gt, const float* pr) {
   double Vs[3][3], U[3][3];
   for (int i = 0; i < 3; ++i)
     for (int r = 0; r < 3; ++r) Vs[r][i] = V[r][o[i]];
-  for (int i = 0; i < 2; ++i) {                          // U_i = K V_i / |K V_i|
-    double u[3], n = 0;
-    for (int r = 0; r < 3; ++r) { u[r] = K[r][0] * Vs[0][i] + K[r][1] * Vs[1][i] + K[r][2] * Vs[2][i]; n += u[r] * u[r]; }
-    n = sqrt(n);
-    for (int r = 0; r < 3; ++r) U[r][i] = n > 0 ? u[r] / n : (r == i ? 1.0 : 0.0);
+  // U is an orthonormal frame whatever the rank of K.  U_0 = K V_0 / |K V_0| (e_x when K = 0: scale is 0 or NaN then and the
+  // frame does not matter).  U_1 = K V_1 made orthogonal to U_0; when what is left is below 1e-10 |K V_0| -- K has rank 1: the
+  // predicted or the ground-truth joints lie on a line, and K V_1 is zero or rounding noise parallel to U_0 -- the unit axis
+  // least aligned with U_0 takes its place.  Any orthonormal completion gives the same error there, as for LAPACK's.
+  double u0[3], u1[3], n0 = 0;
+  for (int r = 0; r < 3; ++r) {
+    u0[r] = K[r][0] * Vs[0][0] + K[r][1] * Vs[1][0] + K[r][2] * Vs[2][0];
+    u1[r] = K[r][0] * Vs[0][1] + K[r][1] * Vs[1][1] + K[r][2] * Vs[2][1];
+    n0 += u0[r] * u0[r];
+  }
+  n0 = sqrt(n0);
+  for (int r = 0; r < 3; ++r) U[r][0] = n0 > 0 ? u0[r] / n0 : (r == 0 ? 1.0 : 0.0);
+  for (int pass = 0; pass < 2; ++pass) {
+    double n1 = 0;
+    for (int again = 0; again < 2; ++again) {            // Gram-Schmidt twice: the first pass may cancel almost everything
+      const double d = u1[0] * U[0][0] + u1[1] * U[1][0] + u1[2] * U[2][0];
+      for (int r = 0; r < 3; ++r) u1[r] -= d * U[r][0];
+    }
+    for (int r = 0; r < 3; ++r) n1 += u1[r] * u1[r];
+    n1 = sqrt(n1);
+    if (pass == 1 || (n0 > 0 && n1 > 1e-10 * n0)) {
+      for (int r = 0; r < 3; ++r) U[r][1] = u1[r] / n1;
+      break;
+    }
+    int ax = 0;
+    for (int r = 1; r < 3; ++r)
+      if (fabs(U[r][0]) < fabs(U[ax][0])) ax = r;
+    for (int r = 0; r < 3; ++r) u1[r] = r == ax ? 1.0 : 0.0;
   }
   U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1];      // U_3 = U_1 x U_2  (det U = +1)
   U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1];

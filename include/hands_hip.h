@@ -566,6 +566,11 @@ int hands_flash_attention_f32(const float* q, const float* k, const float* v, co
  * NaN conventions as the reference (invalid hand -> NaN, except the PA error which it multiplies
  * by the validity flag).  All arrays fp32: joints (B,21,3), 2-D joints (B,21,2) in pixels,
  * per-sample flags (B), per-joint flags (B,21).
+ * Rank-deficient Procrustes: the alignment is a proper rotation whatever the rank of the cross-covariance of the two hands.
+ * Planar joints (rank 2) and joints on a line (rank 1, predicted or ground truth) give the error of the reference's LAPACK
+ * SVD, which there does not depend on how the singular frame is completed; a constant prediction gives NaN (the scale is
+ * 0 / 0, as in the reference), a constant ground truth 0.  The joints of an invalid hand are still read (the PA error is
+ * multiplied by the flag): they must be finite for the 0 to come out, as in the reference.
  * --------------------------------------------------------------------------------------------- */
 typedef struct hands_eval_in {
   const float *pred_j3d_r, *pred_j3d_l, *gt_j3d_r, *gt_j3d_l;

@@ -1,5 +1,6 @@
-"""Plain float64 restatements of the non-convolution kernels of csrc/handocc.hip, csrc/transformer.hip, csrc/vit_b.hip and of
-the layout / pool kernels of csrc/elementwise.hip, for tests/test_gpu_kernel_edges.py.
+"""Plain float64 restatements of the non-convolution kernels of csrc/handocc.hip, csrc/transformer.hip, csrc/vit_b.hip,
+csrc/metrics.hip and csrc/elementwise.hip, for tests/test_gpu_kernel_edges.py and tests/test_gpu_io_edges.py (csrc/frontend.hip
+has its restatement in oracle/frontend_oracle.py).
 
 One function per C entry point of include/hands_hip.h, named after it without ``hands_`` and ``_f32``.  Each takes the entry
 point's arguments in its order -- CPU tensors where the C function takes pointers, with the same layouts (NHWC maps, token rows,
@@ -12,6 +13,7 @@ not re-derived.  tests/test_kernel_refs.py pins every function here to the ATen 
 nothing here is imported by the package.
 """
 import torch
+import torch.nn.functional as F
 
 from oracle import hamer_oracle as H
 from oracle import handoccnet_oracle as HO
@@ -231,3 +233,181 @@ def sumpool_nhwc(feat, B, HW, C, out_stride):
 
 def avgpool_nhwc(feat, B, HW, C, out_stride):
     return _d(feat).view(B, HW, C).sum(1) / HW
+
+
+# ---- csrc/elementwise.hip: the glue kernels ---------------------------------------------------------------------------------
+def _pos_enc(angle, n_freq):
+    """oracle.hands_oracle.pos_enc without its final rounding to float32: (bz, c) -> (bz, n_freq * c * 2), element
+    (k c + ci) 2 + {0: sin, 1: cos} of 2^k angle[ci].  2^k times a float32 angle is exact in float32 and in float64."""
+    bz, c = angle.shape
+    a = (2.0 ** torch.arange(n_freq, dtype=_DT)).view(1, n_freq, 1) * angle.view(bz, 1, c)
+    return torch.stack([torch.sin(a), torch.cos(a)], -1).reshape(bz, -1)
+
+
+def image_posenc_nhwc(img_nchw, center_angle, corner_angle, B, H, W, n_freq, mode, Cpad):
+    """-> (B, H, W, Cpad): [r g b | center encoding if mode & 1 | corner encoding if mode & 2 | zeros]."""
+    parts = [_d(img_nchw).view(B, 3, H, W).permute(0, 2, 3, 1)]
+    if mode & 1:
+        parts.append(_pos_enc(_d(center_angle).view(B, 2), n_freq).view(B, 1, 1, -1).expand(B, H, W, -1))
+    if mode & 2:
+        parts.append(_pos_enc(_d(corner_angle).view(B, 8), n_freq).view(B, 1, 1, -1).expand(B, H, W, -1))
+    out = _zeros(B, H, W, Cpad)
+    cat = torch.cat(parts, -1)
+    out[..., :cat.shape[-1]] = cat
+    return out
+
+
+def kpe_concat(crop, glb, center_angle, corner_angle, B2, Bg, HW, C, n_freq):
+    """-> (B2, HW, C + 20 n_freq): [crop (+ glb of sample b2 % Bg) | center encoding | corner encoding]."""
+    feat = _d(crop).view(B2, HW, C)
+    if glb is not None:
+        feat = feat + _d(glb).view(Bg, HW, C)[torch.arange(B2) % Bg]
+    enc = torch.cat([_pos_enc(_d(center_angle).view(B2, 2), n_freq), _pos_enc(_d(corner_angle).view(B2, 8), n_freq)], 1)
+    return torch.cat([feat, enc.view(B2, 1, -1).expand(B2, HW, -1)], -1)
+
+
+def dense_posenc(angle, mask, img_nchw, B, Ca, Hs, Ws, n_freq, R, Ho, Wo, ld, c_off):
+    """-> with img (B, Ho, Wo, ld): [r g b | encoding | zeros]; without (B, Ho, Wo, Cenc): the columns c_off.. the kernel writes.
+    The masked encoding (n_freq 0: the masked maps themselves) resized to (R, R) and then to (Ho, Wo), both times as
+    F.interpolate(mode='bilinear', align_corners=True) does."""
+    ang, msk = _d(angle).view(B, Ca, Hs, Ws), _d(mask).view(B, 1, Hs, Ws)
+    if n_freq:
+        a = (2.0 ** torch.arange(n_freq, dtype=_DT)).view(1, n_freq, 1, 1, 1) * ang.view(B, 1, Ca, Hs, Ws)
+        enc = torch.stack([torch.sin(a), torch.cos(a)], 3).reshape(B, 2 * n_freq * Ca, Hs, Ws)      # channel (k Ca + ci) 2 + sc
+    else:
+        enc = ang
+    enc = F.interpolate(enc * msk, size=(R, R), mode="bilinear", align_corners=True)
+    enc = F.interpolate(enc, size=(Ho, Wo), mode="bilinear", align_corners=True).permute(0, 2, 3, 1)
+    if img_nchw is None:
+        return enc.contiguous()
+    out = _zeros(B, Ho, Wo, ld)
+    out[..., :3] = _d(img_nchw).view(B, 3, Ho, Wo).permute(0, 2, 3, 1)
+    out[..., 3:3 + enc.shape[-1]] = enc
+    return out
+
+
+def concat_nhwc(a, lda, Ca, add, ld_add, extra, extra_batch_stride, Cb, ld, B, Bg, HW):
+    """-> (B, HW, ld): [a[:, :, :Ca] (+ add of sample b % Bg) | extra (B, HW, Cb), or one (HW, Cb) map for all when the batch
+    stride is 0 | zeros]."""
+    out = _zeros(B, HW, ld)
+    out[..., :Ca] = _d(a).view(B, HW, lda)[..., :Ca]
+    if add is not None:
+        out[..., :Ca] += _d(add).view(Bg, HW, ld_add)[torch.arange(B) % Bg][..., :Ca]
+    if Cb:
+        ex = _d(extra).reshape(-1)
+        idx = (torch.arange(B) * extra_batch_stride).view(B, 1, 1) + torch.arange(HW * Cb).view(1, HW, Cb)
+        out[..., Ca:Ca + Cb] = ex[idx]
+    return out
+
+
+def upsample_bilinear_ac(x, B, h, w, H, W, C):
+    y = F.interpolate(_d(x).view(B, h, w, C).permute(0, 3, 1, 2), size=(H, W), mode="bilinear", align_corners=True)
+    return y.permute(0, 2, 3, 1).contiguous()
+
+
+def rot_leftmul(rotmat, rot, B):
+    """-> (B, 16, 3, 3): joint 0 left-multiplied by rot (B, 3, 3), the other fifteen as they were."""
+    out = _d(rotmat).view(B, 16, 3, 3).clone()
+    out[:, 0] = _d(rot).view(B, 3, 3) @ out[:, 0]
+    return out
+
+
+def perspective_correction(rot_swapped, rotmat, center_angle, is_flipped, Bg):
+    """-> (rot_swapped, rotmat) afterwards, (2 Bg, 16, 3, 3) each: joint 0 of rot_swapped left-multiplied by
+    oracle.hands_oracle.euler_angles_to_matrix_xyz(-center_x, -center_y, 0); rotmat receives the same matrix only when no sample
+    is flipped."""
+    c = _d(center_angle).view(2 * Bg, 2)
+    e = O.euler_angles_to_matrix_xyz(torch.cat([-c, torch.zeros(2 * Bg, 1, dtype=_DT)], -1))
+    sw, un = _d(rot_swapped).view(2 * Bg, 16, 3, 3).clone(), _d(rotmat).view(2 * Bg, 16, 3, 3).clone()
+    sw[:, 0] = e @ sw[:, 0]
+    if not bool((is_flipped != 0).any()):
+        un[:, 0] = sw[:, 0]
+    return sw, un
+
+
+def hmr_init(state, cam_init, B, ld, F_):
+    """-> state (B, ld) afterwards: columns F.. = [identity 6-D x 16 | zeros 10 | 0 0 | cam_init[:, :3] | 0]; the rest untouched."""
+    out = _d(state).view(B, ld).clone()
+    vec = _zeros(B, 112)
+    vec[:, 0:96:6] = 1.0
+    vec[:, 4:96:6] = 1.0
+    vec[:, 108:111] = _d(cam_init).view(B, 4)[:, :3]
+    out[:, F_:F_ + 112] = vec
+    return out
+
+
+def rot6d_to_matrix(pose6d, ld6, B):
+    """-> (B, 16, 3, 3); oracle.hands_oracle.rotation_6d_to_matrix (rows) on the first 96 floats of each row."""
+    return O.rotation_6d_to_matrix(_d(pose6d).view(B, ld6)[:, :96].reshape(-1, 6)).view(B, 16, 3, 3)
+
+
+def grasp_input(shape, ld_shape, rotmat, feat_vec, B2, Bg, F_, ld_out):
+    """-> (B2, ld_out): [feat_vec of sample b % Bg (F) | rotmat 144 | shape 10 | zeros]."""
+    out = _zeros(B2, ld_out)
+    if F_:
+        out[:, :F_] = _d(feat_vec).view(-1)[:Bg * F_].view(Bg, F_)[torch.arange(B2) % Bg]
+    out[:, F_:F_ + 144] = _d(rotmat).view(B2, 144)
+    out[:, F_ + 144:F_ + 154] = _d(shape).view(B2, ld_shape)[:, :10]
+    return out
+
+
+# ---- csrc/metrics.hip -------------------------------------------------------------------------------------------------------
+def _procrustes_mean_error(gt, pr):
+    """eval_modules.py:136-219 on root-aligned (B, 21, 3) joints: mean_j |gt_j - (s R pr_j + t)| with the similarity transform of
+    the reference, LAPACK SVD and its Z[-1, -1] *= sign(det(U V^T))."""
+    mu1, mu2 = pr.mean(1, keepdim=True), gt.mean(1, keepdim=True)
+    X1, X2 = pr - mu1, gt - mu2
+    var1 = (X1 ** 2).sum((1, 2))
+    K = X1.transpose(1, 2) @ X2
+    U, _, Vh = torch.linalg.svd(K)
+    V = Vh.transpose(1, 2)
+    Z = torch.eye(3, dtype=K.dtype).repeat(K.shape[0], 1, 1)
+    Z[:, 2, 2] = torch.sign(torch.linalg.det(U @ V.transpose(1, 2)))
+    Rm = V @ Z @ U.transpose(1, 2)
+    scale = (Rm @ K).diagonal(dim1=1, dim2=2).sum(1) / var1                  # 0 / 0 = NaN for a constant prediction
+    t = mu2.transpose(1, 2) - scale.view(-1, 1, 1) * (Rm @ mu1.transpose(1, 2))
+    hat = scale.view(-1, 1, 1) * (Rm @ pr.transpose(1, 2)) + t
+    return (gt - hat.transpose(1, 2)).norm(dim=2).mean(1)
+
+
+def _nanmean2(a, b):
+    st = torch.stack([a, b], 1)
+    nan = torch.isnan(st)
+    return torch.where(nan, torch.zeros_like(st), st).sum(1) / (~nan).sum(1).to(st.dtype)
+
+
+def eval_metrics(pred_j3d_r, pred_j3d_l, gt_j3d_r, gt_j3d_l, pred_j2d_r, pred_j2d_l, gt_j2d_r, gt_j2d_l, is_valid, right_valid,
+                 left_valid, joints_valid_r, joints_valid_l, B):
+    """The members of hands_eval_in in their order -> those of hands_eval_out in theirs: (mpjpe_ra_h, mpjpe_pa_ra_r, mpjpe_pa_ra_l,
+    mpjpe_pa_ra_h, mrrpe_rl) (B) each in mm, (pix_err_r, pix_err_l) (B, 21) in px.  The root alignment is done in float32, as by
+    the reference and the kernel (the inputs are float32 and that subtraction is part of the definition); everything after it in
+    float64."""
+    f32 = lambda t, *s: t.detach().cpu().to(torch.float32).view(B, *s)
+    nan = float("nan")
+    iv = f32(is_valid)
+    rv, lv = _d(f32(right_valid) * iv), _d(f32(left_valid) * iv)
+    pr, pl, gr, gl = (f32(t, 21, 3) for t in (pred_j3d_r, pred_j3d_l, gt_j3d_r, gt_j3d_l))
+    ra = lambda x: _d(x - x[:, :1])
+    ra_err = lambda g, p, v: torch.where(v != 0, (ra(g) - ra(p)).norm(dim=2).mean(1), torch.full_like(v, nan))
+    mpjpe_ra_h = _nanmean2(ra_err(gr, pr, rv), ra_err(gl, pl, lv)) * 1000.0
+    pa_r, pa_l = _procrustes_mean_error(ra(gr), ra(pr)) * rv, _procrustes_mean_error(ra(gl), ra(pl)) * lv
+    rel = ((_d(pl[:, 0]) - _d(pr[:, 0])) - (_d(gl[:, 0]) - _d(gr[:, 0]))).norm(dim=1)
+    mrrpe = torch.where(lv * rv != 0, rel * 1000.0, torch.full_like(rel, nan))
+    pix = []
+    for g2, p2, jv, v in ((gt_j2d_r, pred_j2d_r, joints_valid_r, rv), (gt_j2d_l, pred_j2d_l, joints_valid_l, lv)):
+        d = (_d(f32(g2, 21, 2)) - _d(f32(p2, 21, 2))).norm(dim=2)
+        pix.append(torch.where(_d(f32(jv, 21)) * v.view(B, 1) != 0, d, torch.full_like(d, nan)))
+    return mpjpe_ra_h, pa_r * 1000.0, pa_l * 1000.0, _nanmean2(pa_r, pa_l) * 1000.0, mrrpe, pix[0], pix[1]
+
+
+def gt_targets(joints, verts, j3d_full, K, img_res, B, NV):
+    """-> (v3d_cam (B, NV, 3), cam_t (B, 3), cam_t_wp (B, 3)): process_data_light as oracle.wrapper_oracle states it."""
+    jc, jf, Km = _d(joints).view(B, 21, 3), _d(j3d_full).view(B, 21, 3), _d(K).view(B, 3, 3)
+    cam_t = jf[:, 0] - jc[:, 0]
+    f = (Km[:, 0, 0] + Km[:, 1, 1]) / 2.0
+    wp = torch.stack([2 * f / (_f32(img_res) * cam_t[:, 2] + 1e-9), cam_t[:, 0], cam_t[:, 1]], -1)
+    return _d(verts).view(B, NV, 3) + (jf - jc).mean(1)[:, None, :], cam_t, wp
+
+
+def unnormalize_kp2d(x, n, img_res):
+    return 0.5 * _f32(img_res) * (_d(x).reshape(-1)[:n] + 1)

@@ -1,5 +1,5 @@
-"""Edge shapes of the non-convolution kernels (csrc/handocc.hip, csrc/transformer.hip, csrc/vit_b.hip, the layout and pool kernels
-of csrc/elementwise.hip) through the C ABI, every output element against the float64 restatements of tests/kernel_refs.py.
+"""Edge shapes of the non-convolution kernels (csrc/handocc.hip, csrc/transformer.hip, csrc/vit_b.hip, csrc/elementwise.hip: its
+layout and pool kernels first, its glue kernels at the end) through the C ABI, every output element against the float64 restatements of tests/kernel_refs.py.
 
 The model-shape tests of these kernels (test_gpu_handoccnet.py, test_gpu_hamer.py, test_gpu_vit_backbone.py, test_gpu_parity.py)
 stay below every launch cap and on every tile boundary.  The cases here are the smallest that reach what those leave out: a
@@ -20,82 +20,16 @@ import torch
 import torch.nn.functional as F
 
 import kernel_refs as R
+from edge_util import BAND, DEV, EINVAL, SENT, Out, _close, _dev, _exact, _gen, _rule
 from hands_amd import _lib
 from hands_amd._lib import check, ptr
+from oracle import hands_oracle as O
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-EINVAL = 10001
-SENT = -7777.25       # exactly representable; no kernel here produces it
-BAND = 256            # floats of sentinel on either side of an output
 
 
 def _stream():
     return torch.cuda.current_stream().cuda_stream
-
-
-def _gen(*key):
-    return torch.Generator().manual_seed(hash(tuple(int(k * 1000) if isinstance(k, float) else k for k in key)) % (2 ** 31))
-
-
-def _dev(*ts):
-    return [t.to(DEV).contiguous() for t in ts]
-
-
-class Out:
-    """A device output of `shape` inside a buffer with a sentinel band on both sides.  The body starts as NaN (or as `init`, for
-    an in-place kernel, or with the sentinel where `keep` is True: padding the kernel must not touch)."""
-
-    def __init__(self, *shape, init=None, keep=None):
-        self.shape, self.n = shape, math.prod(shape)
-        self.buf = torch.full((2 * BAND + self.n,), SENT, device=DEV)
-        body = self.buf[BAND:BAND + self.n].view(shape)
-        if init is not None:
-            body.copy_(init)
-        else:
-            body.fill_(float("nan"))
-        self.keep = keep
-        if keep is not None:
-            body[keep.to(DEV).expand(shape)] = SENT
-
-    def ptr(self):
-        return ptr(self.buf, BAND)
-
-    def get(self):
-        """-> the body on the CPU, after checking the bands and the kept padding."""
-        torch.cuda.synchronize()
-        h = self.buf.cpu()
-        assert torch.all(h[:BAND] == SENT), "wrote in front of the output"
-        assert torch.all(h[BAND + self.n:] == SENT), "wrote behind the output"
-        body = h[BAND:BAND + self.n].view(self.shape)
-        if self.keep is not None:
-            assert torch.all(body[self.keep.expand(self.shape)] == SENT), "wrote into padding"
-        return body
-
-
-def _close(kernel, case, got, ref, bound):
-    assert got.dtype == torch.float32 and got.shape == ref.shape, (kernel, case, got.shape, ref.shape)
-    assert not torch.isnan(got).any(), (kernel, case, "NaN left in the written region")
-    err = (got.double() - ref.double()).abs().max().item()
-    print(f"EDGE|{kernel}|{case}|{err:.3e}|{bound:.3e}")
-    assert err <= bound, (kernel, case, err, bound)
-
-
-def _exact(kernel, case, got, expr32, ref):
-    """Bit-equal to the float32 torch expression, which itself sits within float32 rounding of the float64 restatement: at most
-    three additions, each rounded by half an ulp (2^-24 relative) of an intermediate no larger than twice the largest result."""
-    assert expr32.dtype == torch.float32
-    _close(kernel, case, got, ref, 6 * 2.0 ** -24 * max(1.0, ref.abs().max().item()))
-    assert torch.equal(got, expr32.view(got.shape)), (kernel, case)
-
-
-def _rule(existing, ref, fn, *args):
-    """max(existing bound, 4 x the error of ATen's float32 evaluation of the restatement `fn` against `ref`)."""
-    with R.precision(torch.float32):
-        f32 = fn(*args)
-    assert f32.dtype == torch.float32
-    e32 = (f32.double() - ref).abs().max().item()
-    return max(existing, 4 * e32), e32
 
 
 # ---- streaming kernels: one case past the grid cap by a partial pass, one at the smallest legal size -------------------------------
@@ -657,4 +591,300 @@ def test_elementwise_entry_points_reject_what_is_outside_their_contract():
         assert fn(x, o, 1, 0, 8, 8, st) == EINVAL                                                      # HW = 0
         assert fn(x, o, 1, 4, 6, 8, st) == EINVAL
         assert fn(x, o, 1, 4, 8, 10, st) == EINVAL                                                     # out_stride % 4
+    assert s.untouched()
+
+
+# ---- glue kernels of csrc/elementwise.hip: one case past the grid cap by a partial pass, one at the smallest legal size ---------------
+def _angles(B, n_freq, g):
+    """0.5 * randn angles as the model-shape tests; for n_freq = 16 |angle| <= 1e-3, which keeps 2^15 * angle within 33 rad."""
+    if n_freq < 16:
+        return 0.5 * torch.randn(B, 2, generator=g), 0.5 * torch.randn(B, 8, generator=g)
+    return 1e-3 * (2 * torch.rand(B, 2, generator=g) - 1), 1e-3 * (2 * torch.rand(B, 8, generator=g) - 1)
+
+
+@pytest.mark.parametrize("B,H,W,n_freq,mode,Cpad", [(3, 97, 89, 4, 3, 84), (2, 5, 5, 4, 1, 20), (2, 5, 5, 4, 2, 68), (1, 1, 1, 1, 1, 8),
+                                                    (2, 5, 5, 16, 3, 324)])
+def test_image_posenc(B, H, W, n_freq, mode, Cpad):
+    """(3,97,89) x 21 float4 = 543 879 items.  Encodings at the bound of test_kpe_concat_vs_oracle; image and padding bit-equal."""
+    L = _lib.lib()
+    g = _gen(30, B, H, W, n_freq, mode)
+    img = torch.randn(B, 3, H, W, generator=g)
+    ce, co = _angles(B, n_freq, g)
+    d = _dev(img, ce, co)
+    o = Out(B, H, W, Cpad)
+    check(L.hands_image_posenc_nhwc_f32(ptr(d[0]), ptr(d[1]) if mode & 1 else None, ptr(d[2]) if mode & 2 else None, o.ptr(), B, H, W,
+                                        n_freq, mode, Cpad, _stream()), "image_posenc")
+    got = o.get()
+    _close("image_posenc", f"{B}x{H}x{W} n_freq {n_freq} mode {mode} Cpad {Cpad}", got, R.image_posenc_nhwc(img, ce, co, B, H, W, n_freq, mode, Cpad), 1e-6)
+    nenc = (4 * n_freq if mode & 1 else 0) + (16 * n_freq if mode & 2 else 0)
+    assert torch.equal(got[..., :3], img.permute(0, 2, 3, 1)) and torch.all(got[..., 3 + nenc:] == 0)
+
+
+@pytest.mark.parametrize("B2,Bg,HW,C,n_freq,with_glb", [(14, 7, 457, 8, 16, True), (4, 2, 5, 8, 4, False), (2, 1, 1, 4, 1, True)])
+def test_kpe_concat(B2, Bg, HW, C, n_freq, with_glb):
+    """(14,7,457,8,16): 14 x 457 x 82 float4 = 524 636 items."""
+    L = _lib.lib()
+    g = _gen(31, B2, HW, C, n_freq)
+    crop, glb = torch.randn(B2, HW, C, generator=g), torch.randn(Bg, HW, C, generator=g)
+    ce, co = _angles(B2, n_freq, g)
+    d = _dev(crop, glb, ce, co)
+    o = Out(B2, HW, C + 20 * n_freq)
+    check(L.hands_kpe_concat_f32(ptr(d[0]), ptr(d[1]) if with_glb else None, ptr(d[2]), ptr(d[3]), o.ptr(), B2, Bg, HW, C, n_freq,
+                                 _stream()), "kpe_concat")
+    got = o.get()
+    ref = R.kpe_concat(crop, glb if with_glb else None, ce, co, B2, Bg, HW, C, n_freq)
+    case = f"{B2}x{HW}x{C} n_freq {n_freq} glb {with_glb}"
+    _exact("kpe_concat features", case, got[..., :C].contiguous(), crop + glb[torch.arange(B2) % Bg] if with_glb else crop, ref[..., :C])
+    _close("kpe_concat encodings", case, got[..., C:].contiguous(), ref[..., C:], 1e-6)
+
+
+@pytest.mark.parametrize("with_img", [True, False])
+@pytest.mark.parametrize("n_freq", [0, 3])
+@pytest.mark.parametrize("Hs,Ws,Rr,Ho,Wo", [(5, 9, 12, 7, 10), (5, 9, 1, 1, 1), (5, 9, 12, 1, 1), (12, 9, 12, 7, 10), (5, 12, 12, 12, 12)])
+def test_dense_posenc(Hs, Ws, Rr, Ho, Wo, n_freq, with_img):
+    """Non-square source and outputs, both interpolations; R = 1 and Ho = Wo = 1 (the `out > 1` guard of ac_tap); Hs == R on one axis
+    only (that axis copies); Ho == Wo == R (no second interpolation).  n_freq 0: the six raw 'cam_conv' maps, offsets up to +-100."""
+    L = _lib.lib()
+    B, Ca = 2, (2 if n_freq else 6)
+    g = _gen(32, Hs, Ws, Rr, Ho, n_freq)
+    ang = 0.5 * torch.randn(B, Ca, Hs, Ws, generator=g)
+    if not n_freq:
+        ang[:, 2:4] *= 200.0
+    msk = (torch.rand(B, Hs, Ws, generator=g) > 0.3).float()
+    Cenc = 2 * n_freq * Ca if n_freq else Ca
+    img = torch.randn(B, 3, Ho, Wo, generator=g) if with_img else None
+    ld, c_off = ((3 + Cenc + 15) // 16 * 16, 3) if with_img else (Cenc + 8, 4)
+    cols = torch.arange(ld)
+    o = Out(B, Ho, Wo, ld, keep=None if with_img else ((cols < c_off) | (cols >= c_off + Cenc)).view(1, 1, 1, ld))
+    d = _dev(ang, msk) + (_dev(img) if with_img else [None])
+    check(L.hands_dense_posenc_f32(ptr(d[0]), ptr(d[1]), ptr(d[2]), o.ptr(), B, Ca, Hs, Ws, n_freq, Rr, Ho, Wo, ld, c_off, _stream()),
+          "dense_posenc")
+    got = o.get()
+    args = (ang, msk, img, B, Ca, Hs, Ws, n_freq, Rr, Ho, Wo, ld, c_off)
+    ref = R.dense_posenc(*args)
+    enc_ref = ref[..., 3:3 + Cenc] if with_img else ref
+    bound, e32 = _rule(2e-6 * max(1.0, enc_ref.abs().max().item()), ref, R.dense_posenc, *args)
+    case = f"{Hs}x{Ws}->{Rr}->{Ho}x{Wo} n_freq {n_freq} img {with_img}"
+    print(f"EDGE-F32|dense_posenc|{case}|{e32:.3e}")
+    _close("dense_posenc", case, got if with_img else got[..., c_off:c_off + Cenc].contiguous(), ref, bound)
+    if with_img:
+        assert torch.equal(got[..., :3], img.permute(0, 2, 3, 1)) and torch.all(got[..., 3 + Cenc:] == 0)
+
+
+@pytest.mark.parametrize("B,h,w,H,W,C", [(3, 5, 7, 83, 61, 140), (2, 1, 4, 3, 9, 8), (2, 4, 1, 6, 5, 8), (2, 3, 5, 1, 7, 4), (2, 6, 5, 6, 11, 4),
+                                         (1, 1, 1, 1, 1, 4)])
+def test_upsample_bilinear_ac(B, h, w, H, W, C):
+    """(3,5,7)->(83,61) x 35 float4 = 531 615 items; sources of one row / one column, an output of one row, h == H with w != W."""
+    L = _lib.lib()
+    x = torch.randn(B, h, w, C, generator=_gen(33, B, h, w, H, W))
+    dx, = _dev(x)
+    o = Out(B, H, W, C)
+    check(L.hands_upsample_bilinear_ac_f32(ptr(dx), o.ptr(), B, h, w, H, W, C, _stream()), "upsample_bilinear_ac")
+    ref = R.upsample_bilinear_ac(x, B, h, w, H, W, C)
+    bound, e32 = _rule(1e-6, ref, R.upsample_bilinear_ac, x, B, h, w, H, W, C)
+    print(f"EDGE-F32|upsample_bilinear_ac|{B}x{h}x{w}->{H}x{W}x{C}|{e32:.3e}")
+    _close("upsample_bilinear_ac", f"{B}x{h}x{w}->{H}x{W}x{C}", o.get(), ref, bound)
+
+
+@pytest.mark.parametrize("B,Bg,HW,Ca,lda,Cb,ld,ld_add,shared", [(6, 3, 301, 250, 260, 37, 300, 256, False), (6, 3, 301, 250, 260, 37, 300, 0, False),
+                                                             (4, 2, 5, 6, 6, 0, 6, 8, False), (4, 4, 5, 6, 9, 2, 12, 0, True), (1, 1, 1, 1, 1, 0, 1, 0, False)])
+def test_concat_nhwc(B, Bg, HW, Ca, lda, Cb, ld, ld_add, shared):
+    """(6,3,301) x ld 300 = 541 800 items with and without `add`; Cb = 0 with extra == NULL; one (HW, Cb) map shared by the batch
+    (extra_batch_stride 0); a single element.  The columns behind Ca + Cb are zero."""
+    L = _lib.lib()
+    g = _gen(34, B, HW, Ca, Cb, ld_add)
+    a, add = torch.randn(B, HW, lda, generator=g), (torch.randn(Bg, HW, ld_add, generator=g) if ld_add else None)
+    ex = torch.randn(1 if shared else B, HW, Cb, generator=g) if Cb else None
+    stride = 0 if shared or not Cb else HW * Cb
+    d = [t.to(DEV).contiguous() if t is not None else None for t in (a, add, ex)]
+    o = Out(B, HW, ld)
+    check(L.hands_concat_nhwc_f32(ptr(d[0]), lda, Ca, ptr(d[1]), ld_add, ptr(d[2]), stride, Cb, o.ptr(), ld, B, Bg, HW, _stream()), "concat_nhwc")
+    args = (a, lda, Ca, add, ld_add, ex, stride, Cb, ld, B, Bg, HW)
+    with R.precision(torch.float32):
+        e32 = R.concat_nhwc(*args)
+    got = o.get()
+    _exact("concat_nhwc", f"{B}x{HW} Ca {Ca}/{lda} Cb {Cb} ld {ld} add {ld_add} shared {shared}", got, e32, R.concat_nhwc(*args))
+    assert torch.all(got[..., Ca + Cb:] == 0)
+
+
+@pytest.mark.parametrize("B2,Bg,F_,ld_out,ld_shape", [(238, 119, 2048, 2208, 12), (4, 2, 0, 154, 10), (1, 1, 4, 160, 10)])
+def test_grasp_input(B2, Bg, F_, ld_out, ld_shape):
+    """238 x 2208 = 525 504 items; F = 0 at the smallest ld_out."""
+    L = _lib.lib()
+    g = _gen(35, B2, F_, ld_out)
+    shape, rot, fv = torch.randn(B2, ld_shape, generator=g), torch.randn(B2, 144, generator=g), torch.randn(Bg, max(F_, 1), generator=g)
+    d = _dev(shape, rot, fv)
+    o = Out(B2, ld_out)
+    check(L.hands_grasp_input_f32(ptr(d[0]), ld_shape, ptr(d[1]), ptr(d[2]), o.ptr(), B2, Bg, F_, ld_out, _stream()), "grasp_input")
+    args = (shape, ld_shape, rot, fv, B2, Bg, F_, ld_out)
+    with R.precision(torch.float32):
+        e32 = R.grasp_input(*args)
+    _exact("grasp_input", f"{B2}x{ld_out} F {F_}", o.get(), e32, R.grasp_input(*args))
+
+
+@pytest.mark.parametrize("B,F_,ld", [(4682, 4, 120), (1, 0, 112)])
+def test_hmr_init(B, F_, ld):
+    """4682 x 112 = 524 384 items.  The F feature columns and the tail behind the 112 hold the sentinel and keep it."""
+    L = _lib.lib()
+    cam = torch.randn(B, 4, generator=_gen(36, B))
+    dc, = _dev(cam)
+    cols = torch.arange(ld)
+    o = Out(B, ld, keep=((cols < F_) | (cols >= F_ + 112)).view(1, ld))
+    check(L.hands_hmr_init_f32(o.ptr(), ptr(dc), B, ld, F_, _stream()), "hmr_init")
+    got = o.get()[:, F_:F_ + 112].contiguous()
+    state = torch.zeros(B, ld)
+    with R.precision(torch.float32):
+        e32 = R.hmr_init(state, cam, B, ld, F_)[:, F_:F_ + 112].contiguous()
+    _exact("hmr_init", f"{B} F {F_} ld {ld}", got, e32, R.hmr_init(state, cam, B, ld, F_)[:, F_:F_ + 112])
+
+
+@pytest.mark.parametrize("B,ld6", [(32769, 100), (1, 96)])
+def test_rot6d_to_matrix(B, ld6):
+    """32 769 x 16 = 524 304 joints; the four floats behind the 96 are NaN and never read.  Pairs at least 45 degrees apart, as for
+    the columns variant above."""
+    L = _lib.lib()
+    d6 = torch.full((B, ld6), float("nan"))
+    d6[:, :96] = _well_conditioned_6d(B * 16, _gen(37, B, ld6)).view(B, 96)
+    dd, = _dev(d6)
+    o = Out(B, 16, 3, 3)
+    check(L.hands_rot6d_to_matrix_f32(ptr(dd), ld6, o.ptr(), B, _stream()), "rot6d_to_matrix")
+    _close("rot6d_to_matrix", f"{B} ld6 {ld6}", o.get(), R.rot6d_to_matrix(d6, ld6, B), 5e-6)
+
+
+def _bits_equal(a, b):
+    return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+
+
+def test_rot_conversions_second_pass(golden_dir):
+    """The 513 rotations of rot_conversions.npz tiled to 524 365: row i of the two-pass launch is bit-equal to row i % 513 of a
+    one-pass launch on the fixture, which test_device_rot_conversions_vs_reference_fixture pins to the reference."""
+    import os
+
+    import numpy as np
+    L = _lib.lib()
+    d = np.load(os.path.join(golden_dir, "rot_conversions.npz"))
+    n = 524288 + 77
+    for name, fn, src, width in (("matrix_to_axis_angle", L.hands_matrix_to_axis_angle_f32, torch.from_numpy(d["R"]).float().reshape(-1, 9), 3),
+                                 ("axis_angle_to_matrix", L.hands_axis_angle_to_matrix_f32, torch.from_numpy(d["aa_in"]).float().reshape(-1, 3), 9)):
+        m = src.shape[0]
+        idx = torch.arange(n) % m
+        ds, db = _dev(src, src[idx])
+        small, big = Out(m, width), Out(n, width)
+        check(fn(ptr(ds), small.ptr(), m, _stream()), name)
+        check(fn(ptr(db), big.ptr(), n, _stream()), name)
+        gs, gb = small.get(), big.get()
+        assert not torch.isnan(gs).any() and _bits_equal(gb, gs[idx]), name
+        print(f"EDGE|{name}|{n} rows against {m}|0.000e+00|0.000e+00")
+
+
+def _flip_inputs(Bg, g):
+    rot = O.axis_angle_to_matrix(torch.randn(2 * Bg, 16, 3, generator=g))
+    return rot, torch.randn(2 * Bg, 10, generator=g), torch.randn(2 * Bg, 3, generator=g), torch.randn(2 * Bg, 3, generator=g)
+
+
+def _run_flip(fl, ins, Bg):
+    L = _lib.lib()
+    d = _dev(fl, *ins)
+    outs = [Out(2 * Bg, 16, 3, 3), Out(2 * Bg, 10), Out(2 * Bg, 3), Out(2 * Bg, 3)]
+    check(L.hands_flip_swap_f32(*[ptr(t) for t in d], *[o.ptr() for o in outs], Bg, _stream()), "flip_swap")
+    return [o.get() for o in outs]
+
+
+def test_flip_swap_second_pass_and_single_samples():
+    """Bg = 16 385: 524 320 items, a Bg = 5 problem with mixed flags tiled; bit-equal to the small launch, which
+    test_rot6d_and_flip_vs_oracle pins.  Then Bg = 1 unflipped (a copy) and flipped (the other hand, mirrored)."""
+    g = _gen(38)
+    Bg, big = 5, 16385
+    fl = torch.tensor([0, 1, 1, 0, 1])
+    ins = _flip_inputs(Bg, g)
+    small = _run_flip(fl, ins, Bg)
+    idx = torch.arange(big) % Bg
+    rows = torch.cat([idx, idx + Bg])
+    got = _run_flip(fl[idx], [t[rows] for t in ins], big)
+    for name, a, b in zip(("rotmat", "shape", "cam", "cam_init"), got, small):
+        assert not torch.isnan(b).any() and _bits_equal(a, b[rows]), name
+    print(f"EDGE|flip_swap|Bg {big} against Bg {Bg}|0.000e+00|0.000e+00")
+    one = _flip_inputs(1, g)
+    for name, a, b in zip(("rotmat", "shape", "cam", "cam_init"), _run_flip(torch.tensor([0]), one, 1), one):
+        assert _bits_equal(a, b), name
+    rot, shape, cam, cami = _run_flip(torch.tensor([1]), one, 1)
+    aa = O.matrix_to_axis_angle(one[0].double()).clone()
+    aa[..., 1:] *= -1
+    sgn = torch.tensor([1.0, -1.0, 1.0])
+    _close("flip_swap", "Bg 1 flipped", rot, O.axis_angle_to_matrix(aa).flip(0), 2e-6)
+    assert torch.equal(shape, one[1].flip(0)) and torch.equal(cam, one[2].flip(0) * sgn) and torch.equal(cami, one[3].flip(0) * sgn)
+
+
+@pytest.mark.parametrize("B", [1, 129, 300])
+def test_rot_leftmul(B):
+    """One thread, half a block and one, a block and 44 (B threads, never past the cap: it would take 300 MB).  144-float row stride:
+    the fifteen other joints keep their bits."""
+    L = _lib.lib()
+    g = _gen(39, B)
+    rot, fix = O.axis_angle_to_matrix(torch.randn(B, 16, 3, generator=g)), O.axis_angle_to_matrix(torch.randn(B, 3, generator=g))
+    df, = _dev(fix)
+    o = Out(B, 16, 3, 3, init=rot)
+    check(L.hands_rot_leftmul_f32(o.ptr(), ptr(df), B, _stream()), "rot_leftmul")
+    got, ref = o.get(), R.rot_leftmul(rot, fix, B)
+    bound, e32 = _rule(1e-6, ref, R.rot_leftmul, rot, fix, B)
+    print(f"EDGE-F32|rot_leftmul|{B}|{e32:.3e}")
+    _close("rot_leftmul", f"{B}", got, ref, bound)
+    assert _bits_equal(got[:, 1:], rot[:, 1:])
+
+
+@pytest.mark.parametrize("flagged", [False, True])
+@pytest.mark.parametrize("Bg", [1, 129, 300])
+def test_perspective_correction(Bg, flagged):
+    """2 Bg threads, each scanning the Bg flags.  No flag set: `rotmat` receives the corrected joint 0 too; one flag set (the last):
+    `rotmat`, here all sentinel, is left as it was."""
+    L = _lib.lib()
+    g = _gen(40, Bg)
+    rot = O.axis_angle_to_matrix(torch.randn(2 * Bg, 16, 3, generator=g))
+    center = 0.4 * torch.randn(2 * Bg, 2, generator=g)
+    fl = torch.zeros(Bg, dtype=torch.int64)
+    fl[Bg - 1] = int(flagged)
+    dc, dfl = _dev(center, fl)
+    sent = torch.full((2 * Bg, 16, 3, 3), SENT)
+    sw, un = Out(2 * Bg, 16, 3, 3, init=rot), Out(2 * Bg, 16, 3, 3, init=sent)
+    check(L.hands_perspective_correction_f32(sw.ptr(), un.ptr(), ptr(dc), ptr(dfl), Bg, _stream()), "perspective_correction")
+    gs, gu = sw.get(), un.get()
+    rs, _ = R.perspective_correction(rot, sent, center, fl, Bg)
+    bound, e32 = _rule(1e-6, rs, lambda *a: R.perspective_correction(*a)[0], rot, sent, center, fl, Bg)
+    print(f"EDGE-F32|perspective_correction|Bg {Bg} flagged {flagged}|{e32:.3e}")
+    _close("perspective_correction", f"Bg {Bg} flagged {flagged}", gs, rs, bound)
+    assert _bits_equal(gs[:, 1:], rot[:, 1:]) and torch.all(gu[:, 1:] == SENT)
+    assert torch.all(gu[:, 0] == SENT) if flagged else _bits_equal(gu[:, 0], gs[:, 0])
+
+
+def test_glue_entry_points_reject_what_is_outside_their_contract():
+    L, s = _lib.lib(), _Scratch()
+    x, o, o2, st = ptr(s.x), ptr(s.o), ptr(s.o2), _stream()
+    ip = lambda B, H, W, nf, mode, Cp, ce=x, co=x: L.hands_image_posenc_nhwc_f32(x, ce, co, o, B, H, W, nf, mode, Cp, st)
+    assert ip(1, 2, 2, 4, 3, 80) == EINVAL and ip(1, 2, 2, 4, 3, 82) == EINVAL                        # Cpad too small / % 4
+    assert ip(1, 2, 2, 0, 3, 84) == EINVAL and ip(1, 2, 2, 17, 1, 72) == EINVAL and ip(1, 2, 2, 4, 0, 84) == EINVAL and ip(1, 2, 2, 4, 4, 84) == EINVAL
+    assert ip(0, 2, 2, 4, 3, 84) == EINVAL and ip(1, 0, 2, 4, 3, 84) == EINVAL
+    assert ip(1, 2, 2, 4, 1, 20, None) == EINVAL and ip(1, 2, 2, 4, 2, 68, x, None) == EINVAL          # the mode's angles missing
+    dp = lambda Ca, Hs, nf, Rr, Ho, ld, c_off, img=None: L.hands_dense_posenc_f32(x, x, img, o, 1, Ca, Hs, Hs, nf, Rr, Ho, Ho, ld, c_off, st)
+    assert dp(2, 4, 3, 8, 4, 11, 0) == EINVAL and dp(2, 4, 3, 8, 4, 16, 5) == EINVAL                  # ld < c_off + Cenc
+    assert dp(2, 4, 3, 8, 4, 16, 4, x) == EINVAL                                                       # with img c_off is 3
+    assert dp(0, 4, 3, 8, 4, 16, 0) == EINVAL and dp(2, 0, 3, 8, 4, 16, 0) == EINVAL and dp(2, 4, 17, 8, 4, 80, 0) == EINVAL
+    assert dp(2, 4, 3, 0, 4, 16, 0) == EINVAL and dp(2, 4, 3, 8, 0, 16, 0) == EINVAL and dp(2, 4, 3, 8, 4, 16, -1) == EINVAL
+    cc = lambda lda, Ca, add, ld_add, extra, Cb, ld, B=2, Bg=1, HW=4: L.hands_concat_nhwc_f32(x, lda, Ca, add, ld_add, extra, 0, Cb, o, ld, B, Bg, HW, st)
+    assert cc(4, 6, None, 0, None, 0, 8) == EINVAL and cc(6, 6, None, 0, None, 2, 8) == EINVAL        # lda < Ca; Cb without a map
+    assert cc(6, 6, None, 0, x, 2, 7) == EINVAL and cc(6, 6, x, 5, None, 0, 8) == EINVAL              # ld < Ca + Cb; ld_add < Ca
+    assert cc(6, 6, None, 0, None, 0, 8, B=0) == EINVAL and cc(6, 6, None, 0, None, 0, 8, Bg=0) == EINVAL and cc(6, 6, None, 0, None, 0, 8, HW=0) == EINVAL
+    up = lambda h, w, H, W, C: L.hands_upsample_bilinear_ac_f32(x, o, 1, h, w, H, W, C, st)
+    assert up(2, 2, 4, 4, 6) == EINVAL and up(2, 2, 4, 4, 0) == EINVAL and up(0, 2, 4, 4, 4) == EINVAL and up(2, 2, 4, 0, 4) == EINVAL
+    assert L.hands_rot_leftmul_f32(o, x, 0, st) == EINVAL and L.hands_rot_leftmul_f32(o, None, 2, st) == EINVAL
+    assert L.hands_perspective_correction_f32(o, o2, x, x, 0, st) == EINVAL and L.hands_perspective_correction_f32(o, o2, x, None, 2, st) == EINVAL
+    kc = lambda B2, Bg, C, nf: L.hands_kpe_concat_f32(x, x, x, x, o, B2, Bg, 4, C, nf, st)
+    assert kc(2, 1, 6, 4) == EINVAL and kc(2, 1, 8, 0) == EINVAL and kc(2, 1, 8, 17) == EINVAL and kc(0, 1, 8, 4) == EINVAL and kc(2, 0, 8, 4) == EINVAL
+    assert L.hands_hmr_init_f32(o, x, 2, 115, 4, st) == EINVAL and L.hands_hmr_init_f32(o, x, 0, 116, 4, st) == EINVAL   # ld < F + 112
+    assert L.hands_rot6d_to_matrix_f32(x, 96, o, 0, st) == EINVAL and L.hands_rot6d_to_matrix_f32(None, 96, o, 2, st) == EINVAL
+    assert L.hands_flip_swap_f32(x, x, x, x, x, o, o2, o2, o2, 0, st) == EINVAL
+    assert L.hands_flip_swap_f32(x, x, x, x, None, o, o2, o2, o2, 2, st) == EINVAL
+    assert L.hands_grasp_input_f32(x, 10, x, x, o, 2, 1, 4, 157, st) == EINVAL and L.hands_grasp_input_f32(x, 10, x, x, o, 0, 1, 4, 160, st) == EINVAL
+    assert L.hands_grasp_input_f32(x, 10, x, x, o, 2, 0, 4, 160, st) == EINVAL
+    assert L.hands_matrix_to_axis_angle_f32(x, o, 0, st) == EINVAL and L.hands_axis_angle_to_matrix_f32(x, o, 0, st) == EINVAL
+    assert L.hands_axis_angle_to_matrix_f32(None, o, 4, st) == EINVAL
     assert s.untouched()

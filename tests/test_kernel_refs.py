@@ -1,5 +1,8 @@
 """tests/kernel_refs.py against the ATen operators and oracle functions it restates, on the CPU, at ragged shapes of
 tests/test_gpu_kernel_edges.py: a restatement that is wrong at an odd size would hide a kernel bug there, or invent one."""
+import os
+
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
@@ -8,6 +11,8 @@ import kernel_refs as R
 from oracle import hamer_oracle as H
 from oracle import handoccnet_oracle as HO
 from oracle import hands_oracle as O
+from oracle import metrics_oracle as MO
+from oracle import wrapper_oracle as WO
 
 F64 = 1e-12          # two float64 evaluations of one formula in different orders
 
@@ -197,3 +202,150 @@ def test_vit_tail(B, G):
     y = F.layer_norm(x[:, 1:], (C,), gam, bet, R._f32(eps))
     ref = F.avg_pool2d(y.permute(0, 2, 1).reshape(B, C, G, G), 2).permute(0, 2, 3, 1)
     assert (R.vit_tail(x, gam, bet, B, G, C, eps) - ref).abs().max().item() < 1e-11
+
+
+# ---- the glue kernels of csrc/elementwise.hip ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("n_freq", [1, 4, 16])
+def test_pos_enc_and_its_two_concatenations(n_freq):
+    B2, Bg, HW, C = 4, 2, 3, 8
+    ce, co = 1e-3 * _rand(100, B2, 2).float().double(), 1e-3 * _rand(101, B2, 8).float().double()
+    assert torch.equal(R._pos_enc(ce, n_freq).float(), O.pos_enc(ce, n_freq))
+    crop, glb = _rand(102, B2, HW, C), _rand(103, Bg, HW, C)
+    nchw = lambda t: t.permute(0, 2, 1).reshape(t.shape[0], C, HW, 1)
+    ref = O.assemble_features(nchw(crop), nchw(glb).repeat(2, 1, 1, 1), ce, co, n_freq)[..., 0].permute(0, 2, 1)
+    got = R.kpe_concat(crop, glb, ce, co, B2, Bg, HW, C, n_freq)
+    assert got.shape == (B2, HW, C + 20 * n_freq) and torch.equal(got[..., :C], ref[..., :C])
+    assert torch.equal(got[..., C:].float().double(), ref[..., C:])             # the oracle rounds its encodings to float32
+    assert torch.equal(R.kpe_concat(crop, None, ce, co, B2, Bg, HW, C, n_freq)[..., :C], crop)
+    img = _rand(104, B2, 3, 2, 3)
+    for mode, Cpad in ((1, 3 + 4 * n_freq + 5), (2, 3 + 16 * n_freq + 1), (3, 3 + 20 * n_freq + 1)):
+        Cpad = (Cpad + 3) // 4 * 4
+        out = R.image_posenc_nhwc(img, ce, co, B2, 2, 3, n_freq, mode, Cpad)
+        enc = torch.cat(([R._pos_enc(ce, n_freq)] if mode & 1 else []) + ([R._pos_enc(co, n_freq)] if mode & 2 else []), 1)
+        assert out.shape == (B2, 2, 3, Cpad) and torch.equal(out[..., :3], img.permute(0, 2, 3, 1))
+        assert torch.equal(out[:, 1, 2, 3:3 + enc.shape[1]], enc) and torch.all(out[..., 3 + enc.shape[1]:] == 0)
+
+
+@pytest.mark.parametrize("Hs,Ws,R_,Ho,Wo", [(5, 9, 12, 7, 10), (5, 9, 1, 1, 1), (6, 6, 6, 6, 6), (5, 9, 5, 3, 4)])
+def test_dense_posenc(Hs, Ws, R_, Ho, Wo):
+    """Against the oracle's dense_pos_enc / cam_conv_pos_enc (first resize, square) followed by ATen's second resize."""
+    B, Ca, nf = 2, 2, 3
+    ang = _rand(110, B, Ca, Hs, Ws).float().double()
+    msk = (_rand(111, B, Hs, Ws) > -0.5).double()
+    two = lambda t: F.interpolate(t, size=(Ho, Wo), mode="bilinear", align_corners=True).permute(0, 2, 3, 1)
+    got = R.dense_posenc(ang, msk, None, B, Ca, Hs, Ws, nf, R_, Ho, Wo, 16, 4)
+    # the oracle rounds sin / cos to float32 before the mask and the resize: 6e-8 per tap, weights sum to 1
+    assert got.shape == (B, Ho, Wo, 2 * nf * Ca) and (got - two(O.dense_pos_enc(ang, msk, nf, R_).double())).abs().max().item() < 1.2e-7
+    raw = R.dense_posenc(ang, msk, None, B, Ca, Hs, Ws, 0, R_, Ho, Wo, 8, 0)
+    assert (raw - two(O.cam_conv_pos_enc(ang, msk, R_))).abs().max().item() < F64
+    img = _rand(112, B, 3, Ho, Wo)
+    full = R.dense_posenc(ang, msk, img, B, Ca, Hs, Ws, nf, R_, Ho, Wo, 16, 3)
+    assert full.shape == (B, Ho, Wo, 16) and torch.equal(full[..., :3], img.permute(0, 2, 3, 1))
+    assert torch.equal(full[..., 3:15], got) and torch.all(full[..., 15:] == 0)
+
+
+def test_concat_upsample_and_row_assemblies():
+    B, Bg, HW, Ca, lda, Cb, ld, ld_add = 4, 2, 5, 6, 9, 3, 12, 7
+    a, add, ex = _rand(120, B, HW, lda), _rand(121, Bg, HW, ld_add), _rand(122, B, HW, Cb)
+    ref = torch.cat([a[..., :Ca] + add.repeat(2, 1, 1)[..., :Ca], ex, torch.zeros(B, HW, ld - Ca - Cb, dtype=torch.float64)], -1)
+    assert torch.equal(R.concat_nhwc(a, lda, Ca, add, ld_add, ex, HW * Cb, Cb, ld, B, Bg, HW), ref)
+    ref = torch.cat([a[..., :Ca], ex[:1].repeat(B, 1, 1), torch.zeros(B, HW, ld - Ca - Cb, dtype=torch.float64)], -1)
+    assert torch.equal(R.concat_nhwc(a, lda, Ca, None, 0, ex, 0, Cb, ld, B, Bg, HW), ref)
+    assert torch.equal(R.concat_nhwc(a, lda, Ca, None, 0, None, 0, 0, ld, B, Bg, HW)[..., Ca:], torch.zeros(B, HW, ld - Ca, dtype=torch.float64))
+    x = _rand(123, 2, 5, 7, 4)
+    for H_, W_ in ((11, 13), (1, 9), (5, 3)):
+        ref = F.interpolate(_nchw(x), size=(H_, W_), mode="bilinear", align_corners=True)
+        assert torch.equal(_nchw(R.upsample_bilinear_ac(x, 2, 5, 7, H_, W_, 4)), ref)
+    # align_corners written out at one pixel: src = dst (in - 1) / (out - 1)
+    sy, sx = 3 * 4 / 10, 8 * 6 / 12
+    y0, x0 = int(sy), int(sx)
+    ly, lx = sy - y0, sx - x0
+    want = (1 - ly) * ((1 - lx) * x[1, y0, x0] + lx * x[1, y0, min(x0 + 1, 6)]) + ly * ((1 - lx) * x[1, y0 + 1, x0] + lx * x[1, y0 + 1, min(x0 + 1, 6)])
+    assert (R.upsample_bilinear_ac(x, 2, 5, 7, 11, 13, 4)[1, 3, 8] - want).abs().max().item() < F64
+    B2, F_, ldo, lds = 6, 5, 170, 12
+    shape, rot, fv = _rand(124, B2, lds), _rand(125, B2, 16, 3, 3), _rand(126, 3, F_)
+    gi = R.grasp_input(shape, lds, rot, fv, B2, 3, F_, ldo)
+    assert torch.equal(gi, torch.cat([fv.repeat(2, 1), rot.view(B2, 144), shape[:, :10], torch.zeros(B2, ldo - F_ - 154, dtype=torch.float64)], 1))
+    assert torch.equal(R.grasp_input(shape, lds, rot, fv, B2, 3, 0, 154), torch.cat([rot.view(B2, 144), shape[:, :10]], 1))
+    state, cam = _rand(127, 3, 120), _rand(128, 3, 4)
+    st = R.hmr_init(state, cam, 3, 120, 4)
+    ident = O.matrix_to_rotation_6d(torch.eye(3, dtype=torch.float64)).repeat(16)
+    assert torch.equal(st[:, :4], state[:, :4]) and torch.equal(st[:, 116:], state[:, 116:])
+    assert torch.equal(st[:, 4:100], ident.expand(3, 96)) and torch.all(st[:, 100:112] == 0) and torch.equal(st[:, 112:115], cam[:, :3])
+    assert torch.all(st[:, 115] == 0)
+
+
+def test_rotation_restatements():
+    B = 3
+    d6 = _rand(130, B, 100)
+    got = R.rot6d_to_matrix(d6, 100, B)
+    assert torch.equal(got, O.rotation_6d_to_matrix(d6[:, :96].reshape(-1, 6)).view(B, 16, 3, 3))
+    assert (got[0, 0] @ got[0, 0].T - torch.eye(3, dtype=torch.float64)).abs().max().item() < 1e-12
+    assert (got[0, 0, 0] - d6[0, :3] / d6[0, :3].norm()).abs().max().item() < 1e-15      # b1 is the first ROW
+    rot = O.axis_angle_to_matrix(_rand(131, 2 * B, 16, 3))
+    fix = O.axis_angle_to_matrix(_rand(132, 2 * B, 3))
+    lm = R.rot_leftmul(rot, fix, 2 * B)
+    assert (lm[:, 0] - torch.bmm(fix, rot[:, 0])).abs().max().item() < F64 and torch.equal(lm[:, 1:], rot[:, 1:])
+    center = 0.4 * _rand(133, 2 * B, 2)
+    from scipy.spatial.transform import Rotation
+    e = torch.from_numpy(Rotation.from_euler("XYZ", torch.cat([-center, torch.zeros(2 * B, 1, dtype=torch.float64)], -1).numpy()).as_matrix())
+    for flips in ([0, 0, 0], [0, 1, 0]):
+        sw, un = R.perspective_correction(rot, rot, center, torch.tensor(flips), B)
+        assert (sw[:, 0] - e @ rot[:, 0]).abs().max().item() < F64 and torch.equal(sw[:, 1:], rot[:, 1:])
+        assert torch.equal(un, rot if any(flips) else sw)
+
+
+# ---- csrc/metrics.hip ---------------------------------------------------------------------------------------------------------
+_EVAL_IN = ("pred.mano.j3d.cam.r", "pred.mano.j3d.cam.l", "targets.mano.j3d.cam.r", "targets.mano.j3d.cam.l", "pred.mano.j2d.r",
+            "pred.mano.j2d.l", "targets.mano.j2d.r", "targets.mano.j2d.l", "targets.is_valid", "targets.right_valid",
+            "targets.left_valid", "targets.joints_valid_r", "targets.joints_valid_l")
+_EVAL_OUT = ("mpjpe/ra/h", "mpjpe/pa/ra/r", "mpjpe/pa/ra/l", "mpjpe/pa/ra/h", "mrrpe/r/l", "pix_err/r", "pix_err/l")
+
+
+def test_eval_metrics_on_the_reference_fixture(golden_dir):
+    """Against oracle.metrics_oracle.evaluate, which evaluates in float32 where the reference does: its own distance to the
+    fixture is rtol 1e-5 + atol 2e-4 (tests/test_metrics.py); NaN in the same places."""
+    d = np.load(os.path.join(golden_dir, "eval_metrics.npz"))
+    pred = {k[len("in/pred."):]: d[k] for k in d.files if k.startswith("in/pred.")}
+    targets = {k[len("in/targets."):]: d[k] for k in d.files if k.startswith("in/targets.")}
+    ref = MO.evaluate(pred, targets)
+    B = len(d["in/targets.is_valid"])
+    got = R.eval_metrics(*[torch.from_numpy(d["in/" + k]) for k in _EVAL_IN], B)
+    for k, g in zip(_EVAL_OUT, got):
+        assert g.dtype == torch.float64 and g.shape == ref[k].shape, k
+        np.testing.assert_array_equal(np.isnan(g.numpy()), np.isnan(ref[k]), err_msg=k)
+        np.testing.assert_allclose(g.numpy(), ref[k], rtol=1e-5, atol=2e-4, equal_nan=True, err_msg=k)
+        np.testing.assert_allclose(g.numpy(), d["out/" + k], rtol=1e-5, atol=2e-4, equal_nan=True, err_msg=k)
+
+
+def test_procrustes_restatement_on_rank_deficient_hands():
+    """oracle.metrics_oracle.similarity_transform (np.linalg.svd) on joints on a line, both ways round: the error is unique there
+    (it does not depend on how LAPACK completes the singular frame), 128.566 mm for the prediction on a line in any direction."""
+    rng = np.random.default_rng(1)
+    gt = (0.1 * rng.standard_normal((1, 21, 3))).astype(np.float32)
+    a = rng.integers(-64, 64, (1, 21, 1)) / 512
+    a[0, 0] = 0
+    for dvec in ((1, 0, 0), (1, 2, 0), (1, 1, 1), (3, 5, 7)):
+        line = (a * np.array(dvec, np.float64)).astype(np.float32)
+        for g, p in ((gt, line), (line, gt)):
+            g0, p0 = (g - g[:, :1]).astype(np.float64)[0], (p - p[:, :1]).astype(np.float64)[0]
+            want = np.mean(np.sqrt(np.sum((g0 - MO.similarity_transform(p0, g0)) ** 2, axis=1))) * 1000
+            got = R._procrustes_mean_error(torch.from_numpy(g0)[None], torch.from_numpy(p0)[None]).item() * 1000
+            assert abs(got - want) < 1e-9, (dvec, got, want)
+            if p is line:
+                assert abs(got - 128.566210) < 1e-5
+    const = torch.zeros(1, 21, 3, dtype=torch.float64)
+    g0 = torch.from_numpy((gt - gt[:, :1]).astype(np.float64))
+    assert torch.isnan(R._procrustes_mean_error(g0, const)).all() and R._procrustes_mean_error(const, g0).item() == 0.0
+
+
+def test_gt_targets_and_unnormalize():
+    B, NV = 3, 257
+    jc, jf, verts = 0.1 * _rand(140, B, 21, 3), 0.1 * _rand(141, B, 21, 3) + torch.tensor([0.0, 0.0, 0.8]), 0.1 * _rand(142, B, NV, 3)
+    K = torch.eye(3, dtype=torch.float64).repeat(B, 1, 1)
+    K[:, 0, 0], K[:, 1, 1] = 900.0, 1100.0
+    v3d, cam_t, wp = R.gt_targets(jc, verts, jf, K, 224.0, B, NV)
+    assert (v3d - (verts + (jf - jc).mean(1)[:, None])).abs().max().item() < F64 and torch.equal(cam_t, jf[:, 0] - jc[:, 0])
+    assert (wp - WO.perspective_to_weak_perspective(cam_t, torch.full((B,), 1000.0, dtype=torch.float64), 224)).abs().max().item() < F64
+    x = _rand(143, 50)
+    assert torch.equal(R.unnormalize_kp2d(x, 50, 57.0), WO.unnormalize_kp2d(x, 57))
