@@ -1050,6 +1050,8 @@ bool conv_geometry_ok(const hands_conv_desc* d) {
   if (d->Cin % 4 || d->Cout % 4 || d->Kpad % BK || d->Kpad < d->KH * d->KW * d->Cin) return false;
   if (d->Cin != 4 && d->Cin % 16) return false;
   if (d->in_pix_stride < d->Cin || d->out_pix_stride < d->Cout) return false;
+  // every global access is 16 bytes wide (raw_buffer_load_b128, float4 stores): pixel strides are whole float4s
+  if (d->in_pix_stride % 4 || d->out_pix_stride % 4) return false;
   // the output map may not be larger than the one the geometry produces (the padded-convolution k-loop
   // checks every tap against the image; a larger map would still index pixels of the next image / past the end)
   if (d->H + 2 * d->pad < d->KH || d->W + 2 * d->pad < d->KW) return false;
@@ -1065,6 +1067,11 @@ bool conv_geometry_ok(const hands_conv_desc* d) {
     if (!(d->KH == 1 && d->KW == 1 && d->pad == 0) && (d->KH > 15 || d->KW > 15)) return false;
   }
   return true;
+}
+
+// the residual is read in float4s as well; its stride counts only when there is one (0: one row for every pixel)
+bool residual_ok(const hands_conv_desc* d, const float* residual) {
+  return residual == nullptr || (d->res_pix_stride >= 0 && d->res_pix_stride % 4 == 0);
 }
 
 // the branch-free pointwise k-loop (MODE 2 with its source switch out of reach) has no bounds checks: it
@@ -1146,6 +1153,7 @@ extern "C" int hands_conv2d_group_f32(const hands_conv_job* jobs, int n, hands_s
     if (!j.desc || !j.in || !j.w_packed || !j.bias || !j.out || ((j.pre_scale != nullptr) != (j.pre_shift != nullptr))) return HANDS_EINVAL;
     const int c = group_class(j.desc, j.pre_scale != nullptr);
     if (c < 0 || (cls != -2 && c != cls)) return HANDS_EINVAL;        // one instantiation per launch
+    if (!residual_ok(j.desc, j.residual)) return HANDS_EINVAL;
     cls = c;
     fill_plain_args(j.desc, j.in, j.w_packed, j.bias, j.residual, j.out, j.pre_scale, j.pre_shift, g.a[p]);
   }
@@ -1177,7 +1185,7 @@ extern "C" int hands_conv2d_nhwc_f32(const hands_conv_desc* d, const float* in, 
                                      const float* bias, const float* residual, float* out,
                                      hands_stream_t stream) {
   if (!d || !in || !w_packed || !bias || !out) return HANDS_EINVAL;
-  if (!conv_geometry_ok(d)) return HANDS_EINVAL;
+  if (!conv_geometry_ok(d) || !residual_ok(d, residual)) return HANDS_EINVAL;
   ConvArgs a;
   fill_plain_args(d, in, w_packed, bias, residual, out, nullptr, nullptr, a);
   return launch_conv(d, a, false, (d->act & HANDS_MATH_BF16X3) != 0, (hipStream_t)stream);
@@ -1199,7 +1207,7 @@ extern "C" int hands_conv2d_nhwc_streamk_f32(const hands_conv_desc* d, const flo
                                              const float* bias, const float* residual, float* out, void* workspace,
                                              long long workspace_bytes, int epoch, hands_stream_t stream) {
   if (!d || !in || !w_packed || !bias || !out) return HANDS_EINVAL;
-  if (!conv_geometry_ok(d)) return HANDS_EINVAL;
+  if (!conv_geometry_ok(d) || !residual_ok(d, residual)) return HANDS_EINVAL;
   // the stem has its own kernel; a flagged descriptor is not one fp32 chain: both take the plain entry
   if (d->Cin == 4 || (d->act & (HANDS_MATH_BF16X3 | HANDS_SUM_BLOCK128 | HANDS_SUM_BLOCK64 | HANDS_ACC_F64)))
     return hands_conv2d_nhwc_f32(d, in, w_packed, bias, residual, out, stream);
@@ -1221,6 +1229,7 @@ extern "C" int hands_conv1x1_dual_nhwc_f32(const hands_conv_desc* d, const float
     return HANDS_EINVAL;
   if (d->Cin % 16 || Cin2 <= 0 || Cin2 % 16 || d->Cout % 4 || d->Kpad != d->Cin + Cin2) return HANDS_EINVAL;
   if (d->in_pix_stride < d->Cin || in2_pix_stride < Cin2 || d->out_pix_stride < d->Cout || stride2 < 1) return HANDS_EINVAL;
+  if (d->in_pix_stride % 4 || in2_pix_stride % 4 || d->out_pix_stride % 4) return HANDS_EINVAL;    // 16-byte accesses (conv_geometry_ok)
   if ((d->Ho - 1) * stride2 >= H2 || (d->Wo - 1) * stride2 >= W2) return HANDS_EINVAL;
   if ((long long)d->B * d->H * d->W * d->in_pix_stride >= (1LL << 31) ||
       (long long)d->B * H2 * W2 * in2_pix_stride >= (1LL << 31))
@@ -1258,7 +1267,7 @@ int splitk_launch(const hands_conv_desc* d, const float* in, const float* w_pack
   const bool split = S > 1 && workspace && workspace_floats >= (long long)S * M * part_ps * (f64 ? 2 : 1) &&
                      !(f64 && (((uintptr_t)workspace) & 7));
   if (!split && !pre) return hands_conv2d_nhwc_f32(d, in, w_packed, bias, residual, out, stream);
-  if (!in || !w_packed || !bias || !out || !conv_geometry_ok(d) || (split && S > 64)) return HANDS_EINVAL;
+  if (!in || !w_packed || !bias || !out || !conv_geometry_ok(d) || !residual_ok(d, residual) || (split && S > 64)) return HANDS_EINVAL;
   ConvArgs a;
   fill_plain_args(d, in, w_packed, bias, residual, out, pre_scale, pre_shift, a);
   if (split) {

@@ -66,15 +66,31 @@ int hands_ceiling_hbm_read_f32(const float* in, long long n_floats, float* out, 
  * convolutions take KH, KW <= 15 (tap validity is one 15 + 15 bit word per output pixel), Kpad < 2^21, and
  * (256 / (Ho*Wo) + 2) * H * W * in_pix_stride * 4 < 2^31 (the kernels address a tile's inputs with 32-bit
  * byte offsets from the first image the tile touches).
+ *
+ * Layout contract of a descriptor and its buffers (all entry points that take a hands_conv_desc; tests/test_gpu_conv_edges.py):
+ *   - Every global access is 16 bytes wide.  in_pix_stride, out_pix_stride, res_pix_stride (and the dual entry's in2_pix_stride)
+ *     are multiples of 4 floats -- HANDS_EINVAL otherwise -- and `in`, `in2`, `out`, `residual`, `w_packed`, `bias` are 16-byte
+ *     aligned: a PRECONDITION the library cannot check cheaply for device pointers and does not check.  Pointers may sit
+ *     anywhere inside an allocation; only the channels [0, Cin) of an input pixel, [0, Cout) of a residual pixel are read and
+ *     only [0, Cout) of an output pixel is written -- the floats between Cout and out_pix_stride keep their contents.
+ *   - res_pix_stride == 0: `residual` is ONE row of Cout floats added to every output pixel (hamer_light's mean parameters).
+ *   - `residual` may alias `out` exactly -- the same pointer and the same pixel stride (an in-place update: every thread reads
+ *     the residual values of an element before it writes that element) -- but must not overlap it in any other way.
+ *   - Ho, Wo may be smaller than the map the geometry (H, W, KH, KW, stride, pad) produces: the launch computes the top-left
+ *     Ho x Wo corner of that map, B * Ho * Wo pixels stored densely (a larger map is HANDS_EINVAL).
+ *   - Kpad may exceed round_up(KH*KW*Cin, 16) by any multiple of 16: the extra columns of every weight row must be zero (they
+ *     are multiplied with zeros, not skipped).  The single-launch result does not depend on the extra columns; a split-K launch
+ *     cuts the Kpad / 16 k-steps into S shares, so its summation order is a function of (layer, S, Kpad).  Not for a pointwise layer on the `pre` / grouped / dual entries, whose weight
+ *     row is exactly the pixel's channels (Kpad == Cin, dual: Cin + Cin2).
  * --------------------------------------------------------------------------------------------- */
 typedef struct hands_conv_desc {
   int32_t B, H, W, Cin;      /* input  (B,H,W,Cin) */
   int32_t Ho, Wo, Cout;      /* output (B,Ho,Wo,Cout) */
   int32_t KH, KW, stride, pad;
-  int32_t in_pix_stride;     /* floats between consecutive input pixels  (>= Cin)  */
-  int32_t out_pix_stride;    /* floats between consecutive output pixels (>= Cout) */
-  int32_t res_pix_stride;    /* floats between consecutive residual pixels; ignored if residual==NULL */
-  int32_t Kpad;              /* packed weight row length */
+  int32_t in_pix_stride;     /* floats between consecutive input pixels  (>= Cin,  % 4 == 0) */
+  int32_t out_pix_stride;    /* floats between consecutive output pixels (>= Cout, % 4 == 0) */
+  int32_t res_pix_stride;    /* floats between consecutive residual pixels (% 4 == 0; 0 = one row for every pixel); ignored if residual==NULL */
+  int32_t Kpad;              /* packed weight row length (% 16 == 0, >= KH*KW*Cin; columns beyond that are zero) */
   int32_t act;               /* HANDS_ACT_*: epilogue activation after bias (+ residual) */
 } hands_conv_desc;
 

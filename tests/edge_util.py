@@ -1,5 +1,6 @@
-"""What the edge-shape GPU tests (test_gpu_kernel_edges.py, test_gpu_io_edges.py) share: guarded output buffers, seeded inputs
-and the comparisons that print `EDGE|kernel|case|error|bound` before they assert.  A plain module, imported by both."""
+"""What the edge-shape GPU tests (test_gpu_kernel_edges.py, test_gpu_io_edges.py, test_gpu_conv_edges.py) share: guarded output
+buffers, strided and offset inputs, seeded values and the comparisons that print `EDGE|kernel|case|error|bound` before they assert.  A plain
+module, imported by all three."""
 import math
 
 import torch
@@ -54,6 +55,36 @@ class Out:
         if self.keep is not None:
             assert torch.all(body[self.keep.expand(self.shape)] == SENT), "wrote into padding"
         return body
+
+
+def strided(vals, ps, fill):
+    """vals (M, C) -> the flat CPU buffer of M pixels `ps` floats apart, every gap [C, ps) holding `fill` (the last pixel's too)."""
+    M, C = vals.shape
+    assert ps >= C
+    buf = torch.full((M, ps), float(fill), dtype=vals.dtype)
+    buf[:, :C] = vals
+    return buf.reshape(-1)
+
+
+class In:
+    """A device input whose pointer sits `lead` floats (a non-zero multiple of 4) inside its allocation, NaN in front of and
+    behind the values: a kernel that reads outside them poisons its result."""
+
+    def __init__(self, flat, lead=8, tail=64):
+        assert lead > 0 and lead % 4 == 0
+        flat = flat.reshape(-1)
+        self.lead, self.n = lead, flat.numel()
+        h = torch.full((lead + self.n + tail,), float("nan"), dtype=flat.dtype)
+        h[lead:lead + self.n] = flat
+        self.buf = h.to(DEV)
+
+    def ptr(self, off=0):
+        return ptr(self.buf, self.lead + off)
+
+
+def gap_mask(M, ps, C):
+    """keep-mask of an Out(M, ps): True in the gap [C, ps) of every pixel."""
+    return (torch.arange(ps) >= C).view(1, ps).expand(M, ps)
 
 
 def _close(kernel, case, got, ref, bound):

@@ -1,6 +1,7 @@
 """Plain float64 restatements of the non-convolution kernels of csrc/handocc.hip, csrc/transformer.hip, csrc/vit_b.hip,
 csrc/metrics.hip and csrc/elementwise.hip, for tests/test_gpu_kernel_edges.py and tests/test_gpu_io_edges.py (csrc/frontend.hip
-has its restatement in oracle/frontend_oracle.py).
+has its restatement in oracle/frontend_oracle.py), and -- last in the file -- ``conv_ref``, the one restatement of the convolution
+entry points of csrc/conv_igemm.hip on flat, strided buffers for tests/test_gpu_conv_edges.py.
 
 One function per C entry point of include/hands_hip.h, named after it without ``hands_`` and ``_f32``.  Each takes the entry
 point's arguments in its order -- CPU tensors where the C function takes pointers, with the same layouts (NHWC maps, token rows,
@@ -411,3 +412,69 @@ def gt_targets(joints, verts, j3d_full, K, img_res, B, NV):
 
 def unnormalize_kp2d(x, n, img_res):
     return 0.5 * _f32(img_res) * (_d(x).reshape(-1)[:n] + 1)
+
+
+# ---- csrc/conv_igemm.hip ----------------------------------------------------------------------------------------------------
+def _pixels(buf, n, ps, C):
+    """(n, C): channels [0, C) of n pixels that sit `ps` floats apart in the flat buffer `buf` (ps == 0: one row for all)."""
+    idx = torch.arange(n).view(n, 1) * ps + torch.arange(C).view(1, C)
+    return buf.detach().cpu().reshape(-1)[idx]
+
+
+def conv_act(y, act):
+    """The epilogue activation HANDS_ACT_* (low byte of desc.act) in y's dtype."""
+    act &= 0xff
+    if act == 1:
+        return y.clamp_min(0)
+    if act == 2:
+        return y * 0.5 * (1 + torch.erf(y * 0.70710678118654752440))
+    if act == 3:
+        return torch.where(y > 0, y, 0.01 * y)
+    assert act == 0, act
+    return y
+
+
+def conv_ref(d, x, w, bias, res, out, pre=None, dual=None, round_sum=False):
+    """The convolution entry points of include/hands_hip.h (hands_conv2d_nhwc_f32 and its split-K / fused / stream-K / grouped
+    forms, hands_conv2d_nhwc_pre_f32 with ``pre`` = (scale, shift), hands_conv1x1_dual_nhwc_f32 with ``dual`` = (in2, Cin2, H2,
+    W2, stride2, in2_pix_stride)) on FLAT buffers as the C function sees them: ``x``, ``res`` (or None), ``out`` start at the
+    pointers the call gets, ``out`` holding what the buffer held before the call (pass it as ``res`` too for an in-place
+    residual); ``d`` carries the fields of hands_conv_desc; ``w`` is the packed weight [Cout_pad][Kpad], k = (kh, kw, cin), for
+    the dual form [W0 (Cin) | W1 (Cin2)]; columns beyond KH*KW*Cin of a plain layer are zero by contract and not read here.
+
+    -> (expected, A), both of out's shape: the whole buffer after the call -- pixel m = (b, ho, wo) of the (Ho, Wo) top-left
+    corner of the geometry's map at [m * out_pix_stride, + Cout), everything else as it was -- and the magnitude
+    A = conv(|x|, |w|) + |bias| + |res| of every written element (0 elsewhere).  ``pre``: the operand is
+    leaky_relu(x * scale + shift, 0.01) evaluated in float32, as the kernel stages it (bit-identical to hands_bn_leaky_f32 by the
+    header's contract), whatever the precision.  ``round_sum`` (HANDS_ACC_F64): sum + bias is rounded to float32 once, residual
+    and activation follow in float32."""
+    B, H, W, Cin, Ho, Wo, Cout = d.B, d.H, d.W, d.Cin, d.Ho, d.Wo, d.Cout
+    KH, KW, K, M = d.KH, d.KW, d.KH * d.KW * d.Cin, d.B * d.Ho * d.Wo
+    xs = _pixels(x, B * H * W, d.in_pix_stride, Cin)
+    if pre is not None:
+        xs = xs.float() * pre[0].detach().cpu().float().view(1, Cin) + pre[1].detach().cpu().float().view(1, Cin)
+        xs = torch.where(xs > 0, xs, 0.01 * xs)
+    xs = _d(xs).view(B, H, W, Cin).permute(0, 3, 1, 2)
+    wt = _d(w).reshape(-1, d.Kpad)[:Cout]
+    w0 = wt[:, :K].reshape(Cout, KH, KW, Cin).permute(0, 3, 1, 2)
+    y = F.conv2d(xs, w0, None, d.stride, d.pad)[:, :, :Ho, :Wo]
+    a = F.conv2d(xs.abs(), w0.abs(), None, d.stride, d.pad)[:, :, :Ho, :Wo]
+    assert y.shape[2:] == (Ho, Wo), "the output map is larger than the geometry's"
+    y, a = y.permute(0, 2, 3, 1).reshape(M, Cout), a.permute(0, 2, 3, 1).reshape(M, Cout)
+    if dual is not None:
+        x2, Cin2, H2, W2, s2, ps2 = dual
+        x2 = _d(_pixels(x2, B * H2 * W2, ps2, Cin2)).view(B, H2, W2, Cin2)[:, :(Ho - 1) * s2 + 1:s2, :(Wo - 1) * s2 + 1:s2]
+        x2, w1 = x2.reshape(M, Cin2), wt[:, K:K + Cin2]
+        y, a = y + x2 @ w1.t(), a + x2.abs() @ w1.abs().t()
+    bv = _d(bias).reshape(-1)[:Cout]
+    y, a = y + bv, a + bv.abs()
+    if round_sum:
+        y = y.float()
+    if res is not None:
+        r = _pixels(res, M, d.res_pix_stride, Cout).to(y.dtype)
+        y, a = y + r, a + r.abs().to(a.dtype)
+    y = conv_act(y, d.act).to(_DT)
+    idx = (torch.arange(M).view(M, 1) * d.out_pix_stride + torch.arange(Cout).view(1, Cout)).reshape(-1)
+    exp, mag = _d(out).reshape(-1).clone(), _zeros(out.numel())
+    exp[idx], mag[idx] = y.reshape(-1), a.reshape(-1)
+    return exp.view(out.shape), mag.view(out.shape)

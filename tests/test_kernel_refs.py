@@ -1,5 +1,6 @@
 """tests/kernel_refs.py against the ATen operators and oracle functions it restates, on the CPU, at ragged shapes of
 tests/test_gpu_kernel_edges.py: a restatement that is wrong at an odd size would hide a kernel bug there, or invent one."""
+import math
 import os
 
 import numpy as np
@@ -349,3 +350,159 @@ def test_gt_targets_and_unnormalize():
     assert (wp - WO.perspective_to_weak_perspective(cam_t, torch.full((B,), 1000.0, dtype=torch.float64), 224)).abs().max().item() < F64
     x = _rand(143, 50)
     assert torch.equal(R.unnormalize_kp2d(x, 50, 57.0), WO.unnormalize_kp2d(x, 57))
+
+
+# ---- conv_ref: the convolution entry points (tests/test_gpu_conv_edges.py) ---------------------------------------------------
+class _Desc:
+    """The fields of hands_conv_desc; strides default to the channel counts, the output map to the geometry's, Kpad to K."""
+
+    def __init__(self, B, H, W, Cin, Cout, KH, KW, stride, pad, act=0, Ho=None, Wo=None, in_ps=None, out_ps=None, res_ps=None, Kpad=None):
+        self.B, self.H, self.W, self.Cin, self.Cout, self.KH, self.KW, self.stride, self.pad, self.act = B, H, W, Cin, Cout, KH, KW, stride, pad, act
+        self.Ho = Ho or (H + 2 * pad - KH) // stride + 1
+        self.Wo = Wo or (W + 2 * pad - KW) // stride + 1
+        self.in_pix_stride, self.out_pix_stride = in_ps or Cin, out_ps or Cout
+        self.res_pix_stride = Cout if res_ps is None else res_ps
+        self.Kpad = Kpad or KH * KW * Cin
+
+
+def _conv_bufs(d, seed, res=True, dual=None):
+    """Random flat buffers for `d`: x, packed w [Cout][Kpad] (zero beyond K, or W1 of the dual form), bias, res, out."""
+    K = d.KH * d.KW * d.Cin
+    x = _rand(seed, d.B * d.H * d.W * d.in_pix_stride)
+    w = _rand(seed + 1, d.Cout, d.Kpad)
+    w[:, K + (dual[1] if dual else 0):] = 0
+    bias = _rand(seed + 2, d.Cout)
+    M = d.B * d.Ho * d.Wo
+    r = _rand(seed + 3, max(1, M if d.res_pix_stride else 1) * max(d.res_pix_stride, d.Cout)) if res else None
+    out = _rand(seed + 4, M * d.out_pix_stride)
+    return x, w, bias, r, out
+
+
+def _conv_loops(d, x, w, bias, res, out, pre=None, dual=None):
+    """The header's formula as a loop nest over Python floats: out[m, n] = act(bias[n] + sum_k patch(m, k) w[n, k] (+ res[m, n]))."""
+    x, w, bias, out = x.tolist(), w.tolist(), bias.tolist(), out.clone().tolist()
+    res = None if res is None else res.tolist()
+    leaky = lambda v: v if v > 0 else 0.01 * v
+    for b in range(d.B):
+        for ho in range(d.Ho):
+            for wo in range(d.Wo):
+                m = (b * d.Ho + ho) * d.Wo + wo
+                for n in range(d.Cout):
+                    acc = bias[n]
+                    for kh in range(d.KH):
+                        for kw in range(d.KW):
+                            hi, wi = ho * d.stride - d.pad + kh, wo * d.stride - d.pad + kw
+                            if not (0 <= hi < d.H and 0 <= wi < d.W):
+                                continue
+                            for c in range(d.Cin):
+                                v = x[((b * d.H + hi) * d.W + wi) * d.in_pix_stride + c]
+                                if pre is not None:
+                                    v = leaky(v * pre[0][c].item() + pre[1][c].item())
+                                acc += v * w[n][(kh * d.KW + kw) * d.Cin + c]
+                    if dual is not None:
+                        x2, Cin2, H2, W2, s2, ps2 = dual
+                        for c in range(Cin2):
+                            acc += x2[((b * H2 + ho * s2) * W2 + wo * s2) * ps2 + c].item() * w[n][d.Cin + c]
+                    if res is not None:
+                        acc += res[m * d.res_pix_stride + n]
+                    act = d.act & 0xff
+                    if act == 1:
+                        acc = max(acc, 0.0)
+                    elif act == 2:
+                        acc = acc * 0.5 * (1 + math.erf(acc / math.sqrt(2)))
+                    elif act == 3:
+                        acc = leaky(acc)
+                    out[m * d.out_pix_stride + n] = acc
+    return torch.tensor(out, dtype=torch.float64)
+
+
+CONV_REF_FEATURES = {
+    "plain": dict(),
+    "in_ps": dict(in_ps=7),
+    "out_ps": dict(out_ps=6),
+    "res_ps": dict(res_ps=9),
+    "res_row": dict(res_ps=0),
+    "all_strides": dict(in_ps=8, out_ps=8, res_ps=12),
+    "crop_corner": dict(Ho=2, Wo=3),
+    "crop_row": dict(Ho=1),
+    "crop_pixel": dict(Ho=1, Wo=1),
+    "crop_strided": dict(Ho=2, Wo=2, out_ps=5, in_ps=6),
+    "k1x3": dict(KH=1, KW=3, pad=0),
+    "k3x1": dict(KH=3, KW=1, pad=0),
+    "k5x3": dict(KH=5, KW=3, pad=1, H=6, W=5),
+    "patch_half": dict(KH=2, KW=4, stride=4, pad=0, H=4, W=8, Ho=1),
+    "kpad16": dict(Kpad=36 + 16),
+    "kpad48": dict(Kpad=36 + 48),
+    "stride2_odd": dict(stride=2, H=5, W=7),
+    "pointwise_s2": dict(KH=1, KW=1, pad=0, stride=2, H=5, W=3),
+    "relu": dict(act=1),
+    "gelu": dict(act=2),
+    "leaky": dict(act=3),
+    "flags_ignored": dict(act=3 | 0x400),
+}
+
+
+@pytest.mark.parametrize("name", sorted(CONV_REF_FEATURES))
+@pytest.mark.parametrize("use_res", [False, True])
+def test_conv_ref_against_the_loop_nest(name, use_res):
+    kw = dict(B=2, H=4, W=5, Cin=4, Cout=4, KH=3, KW=3, stride=1, pad=1)
+    kw.update(CONV_REF_FEATURES[name])
+    d = _Desc(**kw)
+    x, w, bias, r, out = _conv_bufs(d, 100, res=use_res)
+    exp, mag = R.conv_ref(d, x, w, bias, r, out)
+    ref = _conv_loops(d, x, w, bias, r, out)
+    assert exp.shape == out.shape and (exp - ref).abs().max().item() < F64
+    written = torch.zeros(out.numel(), dtype=torch.bool)
+    for m in range(d.B * d.Ho * d.Wo):
+        written[m * d.out_pix_stride: m * d.out_pix_stride + d.Cout] = True
+    assert torch.equal(exp[~written], out[~written]) and torch.all(mag[~written] == 0)      # gaps as they were
+    assert torch.all(mag[written] >= exp[written].abs() * (1 - 1e-12))                      # |act(y)| <= |y| <= A
+    ones = R.conv_ref(d, x.abs(), w.abs(), bias.abs(), None if r is None else r.abs(), out)[0 if (d.act & 0xff) != 2 else 1]
+    if (d.act & 0xff) != 2:
+        assert (mag[written] - ones[written]).abs().max().item() < F64                      # A is the result on magnitudes
+
+
+def test_conv_ref_in_place_residual_and_pre_and_dual():
+    d = _Desc(2, 3, 4, 4, 4, 1, 1, 1, 0, act=1, out_ps=6, res_ps=6)
+    x, w, bias, _, out = _conv_bufs(d, 200, res=False)
+    exp, _ = R.conv_ref(d, x, w, bias, out, out)                                            # the residual IS the output buffer
+    assert (exp - _conv_loops(d, x, w, bias, out, out)).abs().max().item() < F64
+    d = _Desc(2, 3, 4, 4, 8, 1, 1, 1, 0, act=3, in_ps=5)
+    x, w, bias, r, out = _conv_bufs(d, 210)
+    pre = (_rand(5, 4).float() + 1.5, _rand(6, 4).float())
+    x = x.float().double()                                                                  # fp32 data: the operand is staged in fp32
+    exp, _ = R.conv_ref(d, x, w, bias, r, out, pre=pre)
+    assert (exp - _conv_loops(d, x, w, bias, r, out, pre=pre)).abs().max().item() < 1e-5    # fp32 operand against fp64 loops
+    op = F.leaky_relu(R._pixels(x, 24, 5, 4).float() * pre[0] + pre[1], 0.01)
+    d2 = _Desc(2, 3, 4, 4, 8, 1, 1, 1, 0, act=3)
+    assert torch.equal(R.conv_ref(d2, op.reshape(-1), w, bias, r, out)[0], exp)             # = hands_bn_leaky_f32, then the layer
+    for s2, H2, W2 in ((1, 3, 4), (2, 5, 7), (2, 6, 8)):
+        d = _Desc(2, 3, 4, 4, 4, 1, 1, 1, 0, act=1, Kpad=4 + 8, in_ps=6, out_ps=5)
+        dual = (_rand(220, 2 * H2 * W2 * 10), 8, H2, W2, s2, 10)
+        x, w, bias, _, out = _conv_bufs(d, 230, res=False, dual=dual)
+        exp, mag = R.conv_ref(d, x, w, bias, None, out, dual=dual)
+        assert (exp - _conv_loops(d, x, w, bias, None, out, dual=dual)).abs().max().item() < F64
+        assert torch.all(mag >= exp.abs() * (1 - 1e-12) * (mag > 0))
+
+
+@pytest.mark.parametrize("B,Cin,H,W,Cout,KH,KW,stride,pad,act", [
+    (3, 16, 5, 11, 140, 3, 3, 1, 1, 1), (2, 32, 9, 7, 20, 1, 1, 2, 0, 3), (2, 4, 9, 11, 64, 7, 7, 2, 3, 1), (1, 48, 6, 8, 12, 5, 3, 1, 2, 2),
+    (2, 16, 8, 16, 8, 8, 16, 16, 0, 0)])
+def test_conv_ref_against_aten(B, Cin, H, W, Cout, KH, KW, stride, pad, act):
+    d = _Desc(B, H, W, Cin, Cout, KH, KW, stride, pad, act=act)
+    x, w, bias, r, out = _conv_bufs(d, 300)
+    wt = w.view(Cout, KH, KW, Cin).permute(0, 3, 1, 2)
+    ref = F.conv2d(_nchw(x.view(B, H, W, Cin)), wt, bias, stride, pad) + _nchw(r.view(B, d.Ho, d.Wo, Cout))
+    ref = {0: lambda t: t, 1: F.relu, 2: F.gelu, 3: lambda t: F.leaky_relu(t, 0.01)}[act](ref)
+    exp, mag = R.conv_ref(d, x, w, bias, r, out)
+    assert (_nchw(exp.view(B, d.Ho, d.Wo, Cout)) - ref).abs().max().item() < F64
+    with R.precision(torch.float32):
+        e32, _ = R.conv_ref(d, x, w, bias, r, out)
+    assert e32.dtype == torch.float32 and (e32.double() - exp).abs().max().item() < 1e-4
+    # HANDS_ACC_F64: one rounding of sum + bias, then residual and activation in float32
+    if act != 2:
+        rs, _ = R.conv_ref(d, x.float(), w.float(), bias.float(), r.float(), out.float(), round_sum=True)
+        s = F.conv2d(_nchw(x.float().double().view(B, H, W, Cin)), wt.float().double(), bias.float().double(), stride, pad).float()
+        s = s + _nchw(r.float().view(B, d.Ho, d.Wo, Cout))
+        s = {0: lambda t: t, 1: F.relu, 3: lambda t: F.leaky_relu(t, 0.01)}[act](s)
+        assert (_nchw(rs.view(B, d.Ho, d.Wo, Cout)) != s.double()).float().mean().item() < 1e-3      # ties of the fp64 sum's order only
