@@ -720,6 +720,13 @@ int hands_warp_affine_cubic_norm_f32(const float* src, const float* trans, float
  *   (the reference: 1e-5 and log(1/1e-6 - 1) * 1e-5); faces_per_pixel nearest candidates are blended, ties to the lower index.
  *   mask (B, S, S) = alpha in [0, 1].  Optional (NULL = not written), from the same pass, over the faces that CONTAIN the pixel:
  *   face_idx (B, S, S) int32, -1 where empty, and zbuf (B, S, S), the screen-space interpolated depth, 0 where empty.
+ *   Every pixel of every output is written, whatever the faces: n_faces = 0 (faces must still be non-NULL) gives mask 0,
+ *   face_idx -1, zbuf 0.  Skipped besides the two kinds above: a face with a NaN vertex, a face whose projected |area| (the edge
+ *   function of its corners, twice the triangle's) is <= 1e-8, collinear ones included; a face with an infinite vertex is a
+ *   candidate at no pixel.  Each of these leaves every output bit-equal to the call without the face.  An edge of squared NDC
+ *   length <= 1e-8 counts as its END point in the distance to the face's outline.  Equal depths: faces are visited in index
+ *   order and a later face replaces an earlier one only when strictly nearer, in the top faces_per_pixel as in face_idx / zbuf;
+ *   the depths of translated copies of a fronto-parallel face are bit-equal.  ld_verts > 3 n_verts: the padding is not read.
  * HANDS_EINVAL (nothing launched): faces_per_pixel outside [1, 10]; a vertex block that does not fit in LDS beside the face
  * list (12 n_verts + 24 608 > 65 536 bytes, i.e. n_verts > 3410); sigma <= 0; blur_radius < 0; S outside [1, 16384].
  * n_faces is unbounded: a tile whose face list overflows its LDS share is processed in chunks.  The tile and the list are
@@ -752,7 +759,12 @@ int hands_render_silhouette_f32(const float* verts, int ld_verts, int n_verts, c
  *   Outputs, each optional (NULL = not written): rgb (B, S, S, 3) floats, rgb8 (B, S, S, 3) = floor(255 clamp(rgb, 0, 1)),
  *   depth (B, S, S) with 0 where empty, face_id (B, S, S) with -1 where empty, else face index + the mesh's face_offset.
  *   scene is a HOST pointer, read before the call returns.  No allocation, no synchronisation: capturable.
- * HANDS_EINVAL (nothing launched): n_meshes outside [1, 4], a NULL workspace / faces, S outside [1, 16384], no output at all.
+ *   A mesh with n_faces = 0 (faces still non-NULL) or valid[b] == 0 draws nothing in image b, wherever it stands among the
+ *   meshes; with nothing to draw every requested output is still written (background, depth 0, face_id -1).  Each output
+ *   requested alone is bit-equal to the same output of a call that requests all four.  A zero interpolated normal (squared
+ *   length <= 1e-30: an empty CSR row, opposite faces) is replaced by the view direction.
+ * HANDS_EINVAL (nothing launched): n_meshes outside [1, 4], a NULL workspace / faces, a workspace that is not 16-byte aligned (both
+ * entries), S outside [1, 16384], no output at all.
  * HANDS_SHADE_TILE_W, _TILE_H and _LIST_CAP are the tile and the face list of csrc/raster_tile.h: hands_render_silhouette_f32
  * uses the same tile and list. */
 #define HANDS_SHADE_MAX_MESHES 4

@@ -1,6 +1,6 @@
-"""What the edge-shape GPU tests (test_gpu_kernel_edges.py, test_gpu_io_edges.py, test_gpu_conv_edges.py) share: guarded output
-buffers, strided and offset inputs, seeded values and the comparisons that print `EDGE|kernel|case|error|bound` before they assert.  A plain
-module, imported by all three."""
+"""What the edge-shape GPU tests (test_gpu_kernel_edges.py, test_gpu_io_edges.py, test_gpu_conv_edges.py,
+test_gpu_raster_edges.py) share: guarded output buffers, strided and offset inputs, seeded values and the comparisons that print
+`EDGE|kernel|case|error|bound` before they assert.  A plain module, imported by all four."""
 import math
 
 import torch
@@ -54,6 +54,33 @@ class Out:
         body = h[BAND:BAND + self.n].view(self.shape)
         if self.keep is not None:
             assert torch.all(body[self.keep.expand(self.shape)] == SENT), "wrote into padding"
+        return body
+
+
+class OutInt:
+    """Out's counterpart for an int32 or uint8 output: sentinel bands of BAND elements on both sides, the body preset to a
+    second value (`unwritten`) that no kernel here produces for int32 (indices are >= -1); for uint8 every value is a legitimate
+    result, so an unwritten element shows only through the caller's comparison with the expected picture."""
+    SENT = {torch.int32: -77777, torch.uint8: 0xA5}
+    UNWRITTEN = {torch.int32: -99999, torch.uint8: 0x5A}
+
+    def __init__(self, dtype, *shape):
+        self.shape, self.n, self.dtype = shape, math.prod(shape), dtype
+        self.sent, self.unwritten = self.SENT[dtype], self.UNWRITTEN[dtype]
+        self.buf = torch.full((2 * BAND + self.n,), self.sent, dtype=dtype, device=DEV)
+        self.buf[BAND:BAND + self.n] = self.unwritten
+
+    def ptr(self):
+        return ptr(self.buf, BAND)
+
+    def get(self):
+        torch.cuda.synchronize()
+        h = self.buf.cpu()
+        assert torch.all(h[:BAND] == self.sent), "wrote in front of the output"
+        assert torch.all(h[BAND + self.n:] == self.sent), "wrote behind the output"
+        body = h[BAND:BAND + self.n].view(self.shape)
+        if self.dtype == torch.int32:
+            assert not torch.any(body == self.unwritten), "an element was left unwritten"
         return body
 
 

@@ -55,6 +55,8 @@ def candidates(verts, faces, K, S, dtype=np.float64, blur_radius=BLUR_RADIUS):
     margin = 2.0 * math.sqrt(max(blur_radius, 0.0)) + 4.0 / S              # window only: a pure speed-up, twice the reach of a candidate
     out = [[], [], [], [], [], []]
     for f, (i0, i1, i2) in enumerate(np.asarray(faces).astype(np.int64)):
+        if min(i0, i1, i2) < 0 or max(i0, i1, i2) >= V.shape[0]:       # an index out of range: skipped
+            continue
         z0, z1, z2 = zz[i0], zz[i1], zz[i2]
         if not (z0 > 0 and z1 > 0 and z2 > 0):
             continue
@@ -93,16 +95,38 @@ def candidates(verts, faces, K, S, dtype=np.float64, blur_radius=BLUR_RADIUS):
     return tuple(np.concatenate(o) for o in out)
 
 
-def render(verts, faces, K, S, dtype=np.float64, sigma=SIGMA, blur_radius=BLUR_RADIUS, faces_per_pixel=FACES_PER_PIXEL):
+def depth_groups(pix, pz, tie_rel):
+    """pix, pz sorted by (pixel, depth) -> a group number per candidate, ascending with (pixel, depth): a candidate starts a
+    new group when its pixel changes or its depth exceeds its predecessor's by more than tie_rel x |depth|."""
+    if pix.size == 0:
+        return np.zeros(0, np.int64)
+    new = np.ones(pix.size, bool)
+    new[1:] = (pix[1:] != pix[:-1]) | (pz[1:] - pz[:-1] > tie_rel * np.abs(pz[1:]))
+    return np.cumsum(new) - 1
+
+
+def render(verts, faces, K, S, dtype=np.float64, sigma=SIGMA, blur_radius=BLUR_RADIUS, faces_per_pixel=FACES_PER_PIXEL,
+           tie_rel=0.0):
     """One hand.  Returns a dict of (S, S) arrays:
     mask, mask_all (every candidate blended: what ignoring faces_per_pixel would give), n_cand, tie_gap (pz of candidate
     faces_per_pixel+1 minus pz of candidate faces_per_pixel, inf where there is no such candidate), face_idx, zbuf, z_gap
-    (second nearest containing depth minus the nearest, inf where there is no second) and win_wmin (smallest barycentric of the
-    winning face, inf where none)."""
+    (second nearest containing depth minus the nearest, inf where there is no second), win_wmin (smallest barycentric of the
+    winning face, inf where none) and top (S, S, faces_per_pixel): the blended faces in blending order, -1 where fewer.
+
+    tie_rel = 0 (the default) orders a pixel's candidates by the computed depth alone, the face index deciding between
+    bit-equal depths only: depths that are equal in exact arithmetic but differ in the last bit are ordered by that rounding.
+    tie_rel > 0 is the tie mode: depths at a pixel that differ by no more than tie_rel x |depth| from their neighbour in depth
+    order count as EQUAL and are ordered by face index (the rule "ties: lower face index" for an implementation whose equal
+    depths are bit-equal); tie_gap and z_gap are then taken between depth groups only (0 never occurs)."""
     pix, face, pz, dist, wmin, ins = candidates(verts, faces, K, S, dtype, blur_radius)
     n = S * S
     order = np.lexsort((face, pz, pix))                      # by pixel, then depth, then face index
     pix, face, pz, dist, wmin, ins = pix[order], face[order], pz[order], dist[order], wmin[order], ins[order]
+    group = None
+    if tie_rel > 0:
+        group = depth_groups(pix, pz, tie_rel)
+        order = np.lexsort((face, group))                    # the group number ascends with the pixel
+        pix, face, pz, dist, wmin, ins, group = (a[order] for a in (pix, face, pz, dist, wmin, ins, group))
     n_cand = np.bincount(pix, minlength=n)
     start = np.concatenate(([0], np.cumsum(n_cand)[:-1]))
     rank = np.arange(pix.size) - start[pix]
@@ -115,9 +139,12 @@ def render(verts, faces, K, S, dtype=np.float64, sigma=SIGMA, blur_radius=BLUR_R
     np.multiply.at(keep_top, pix[top], dt(1) - prob[top])
     tie_gap = np.full(n, np.inf)
     nxt = np.nonzero(rank == faces_per_pixel)[0]
-    tie_gap[pix[nxt]] = pz[nxt] - pz[nxt - 1]
+    tie_gap[pix[nxt]] = pz[nxt] - pz[nxt - 1] if group is None else np.where(group[nxt] == group[nxt - 1], np.inf, pz[nxt] - pz[nxt - 1])
+    top_faces = np.full((n, faces_per_pixel), -1, np.int64)
+    top_faces[pix[top], rank[top]] = face[top]
     # nearest containing face
     ipix, iface, ipz, iw = pix[ins], face[ins], pz[ins], wmin[ins]
+    igroup = None if group is None else group[ins]
     icount = np.bincount(ipix, minlength=n)
     istart = np.concatenate(([0], np.cumsum(icount)[:-1]))
     irank = np.arange(ipix.size) - istart[ipix]
@@ -126,11 +153,17 @@ def render(verts, faces, K, S, dtype=np.float64, sigma=SIGMA, blur_radius=BLUR_R
     first = irank == 0
     face_idx[ipix[first]], zbuf[ipix[first]], win_wmin[ipix[first]] = iface[first], ipz[first], iw[first]
     second = np.nonzero(irank == 1)[0]
-    z_gap[ipix[second]] = ipz[second] - ipz[second - 1]
+    if igroup is None:
+        z_gap[ipix[second]] = ipz[second] - ipz[second - 1]
+    else:                                                    # the nearest containing depth of ANOTHER group
+        win_group = np.full(n, -1, np.int64)
+        win_group[ipix[first]] = igroup[first]
+        other = igroup != win_group[ipix]
+        np.minimum.at(z_gap, ipix[other], ipz[other] - zbuf[ipix[other]])
     sh = lambda a: a.reshape(S, S)
     return {"mask": sh((dt(1) - keep_top).astype(np.float64)), "mask_all": sh((dt(1) - keep_all).astype(np.float64)),
             "n_cand": sh(n_cand), "tie_gap": sh(tie_gap), "face_idx": sh(face_idx), "zbuf": sh(zbuf), "z_gap": sh(z_gap),
-            "win_wmin": sh(win_wmin)}
+            "win_wmin": sh(win_wmin), "top": top_faces.reshape(S, S, faces_per_pixel)}
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -78,6 +78,29 @@ def vertex_normals(P, faces, dtype=np.float64):
     return n
 
 
+def vertex_normals_csr(P, faces, csr_off, csr_face, dtype=np.float64):
+    """Step 1 through the CALLER's vertex -> face table, as hands_mesh_prepare_f32 gathers it: vertex v sums the faces
+    csr_face[csr_off[v] : csr_off[v + 1]] in the order they are listed; an entry outside [0, F), a face with a vertex index out of
+    range and a face whose cross product is not finite add nothing.  An empty row gives the zero vector."""
+    faces, csr_off, csr_face = np.asarray(faces), np.asarray(csr_off), np.asarray(csr_face)
+    acc = np.zeros((P.shape[0], 3), dtype)
+    ok = usable_faces(P, faces) if faces.shape[0] else np.zeros(0, bool)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for v in range(P.shape[0]):
+            for f in csr_face[csr_off[v]:csr_off[v + 1]]:
+                if f < 0 or f >= faces.shape[0] or not ok[f]:
+                    continue
+                i0, i1, i2 = (int(t) for t in faces[f])
+                cr = np.cross(P[i1] - P[i0], P[i2] - P[i0]).astype(dtype)
+                if np.isfinite(cr).all():
+                    acc[v] += cr
+        s2 = (acc * acc).sum(axis=1)
+        good = s2 > dtype(1e-30)
+        n = np.zeros_like(acc)
+        n[good] = acc[good] / np.sqrt(s2[good])[:, None]
+    return n
+
+
 def project(P, K, S, dtype=np.float64):
     K = np.asarray(K).astype(dtype)
     with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
@@ -104,8 +127,14 @@ def brdf(c, metallic, roughness, NdotL, NdotV, NdotH, VdotH, dtype=np.float64):
     return np.clip(col, 0, 1)
 
 
-def render(meshes, K, S, T=None, image=None, dtype=np.float64, tile=None):
-    """One image.  Returns rgb (S, S, 3), image uint8, depth (0 = empty), face_id (-1 = empty; face index + the faces of the
+def render(meshes, K, S, T=None, image=None, dtype=np.float64, tile=None, tie_rel=0.0):
+    """One image.  A mesh may carry "csr": (csr_off, csr_face), the caller's vertex -> face table; its normals are then gathered
+    through it (vertex_normals_csr) instead of summed over all faces.  "n_draw": only the first n_draw faces are drawn (the
+    normals still see them all; face_id counts them all).
+    tie_rel = 0 (the default): a face wins a pixel when its computed depth is smaller, so depths that are equal in exact arithmetic
+    but differ in the last bit are decided by that rounding.  tie_rel > 0 is the tie mode: a face wins only when it is nearer by
+    more than tie_rel x depth; depths closer than that count as EQUAL and stay with the lower (mesh, face), are not `unsure`, and
+    `gap` is the distance to the nearest covering depth that is not equal to the winner's.  Returns rgb (S, S, 3), image uint8, depth (0 = empty), face_id (-1 = empty; face index + the faces of the
     meshes before it, valid or not), covered, unsure (the pixels where a float32 implementation may legitimately decide
     otherwise), gap (distance of the two nearest covering depths) and, with tile=(w, h), tile_candidates (rows, cols): the faces
     whose box meets the tile's sample points."""
@@ -133,6 +162,7 @@ def render(meshes, K, S, T=None, image=None, dtype=np.float64, tile=None):
             continue
         xn, yn = project(P, K, S, dtype)
         ok = usable_faces(P, faces)
+        ok[mesh.get("n_draw", F):] = False
         for f in np.nonzero(ok)[0]:
             i0, i1, i2 = faces[f]
             x0, y0, z0, x1, y1, z1, x2, y2, z2 = xn[i0], yn[i0], P[i0, 2], xn[i1], yn[i1], P[i1, 2], xn[i2], yn[i2], P[i2, 2]
@@ -171,11 +201,18 @@ def render(meshes, K, S, T=None, image=None, dtype=np.float64, tile=None):
                 z = one / (q0 + q1 + q2)
             z = np.where(inside, z, np.inf).astype(dtype)
             bz, sz, bb, bw = best_z[sl], second_z[sl], best[sl], bary[sl]
-            wins = z < bz                                 # strict: equal depths stay with the lower (mesh, face)
-            second_z[sl] = np.where(wins, bz, np.minimum(sz, z))
+            if tie_rel > 0:
+                with np.errstate(invalid="ignore"):
+                    wins = z < np.where(np.isfinite(bz), bz - dtype(tie_rel) * np.abs(bz), bz)
+                    tied = ~wins & (z <= bz + dtype(tie_rel) * np.abs(bz))
+                second_z[sl] = np.where(wins, bz, np.where(tied, sz, np.minimum(sz, z)))
+            else:
+                wins = z < bz                             # strict: equal depths stay with the lower (mesh, face)
+                second_z[sl] = np.where(wins, bz, np.minimum(sz, z))
             best_z[sl] = np.where(wins, z, bz)
             best[sl] = np.where(wins, offset + f, bb)
-            nb = np.stack([q0 * z, q1 * z, q2 * z], axis=-1)
+            with np.errstate(invalid="ignore"):             # 0 x inf outside the face: never selected
+                nb = np.stack([q0 * z, q1 * z, q2 * z], axis=-1)
             bary[sl] = np.where(wins[..., None], nb, bw)
         offset += F
 
@@ -191,7 +228,7 @@ def render(meshes, K, S, T=None, image=None, dtype=np.float64, tile=None):
             sel = (gid >= off) & (gid < off + faces.shape[0])
             if not sel.any() or not mesh.get("valid", True):
                 continue
-            nrm = vertex_normals(P, faces, dtype)
+            nrm = vertex_normals_csr(P, faces, *mesh["csr"], dtype) if "csr" in mesh else vertex_normals(P, faces, dtype)
             tri = faces[gid[sel] - off]
             b = bary[rr[sel], cc[sel]]
             Pp = (b[:, :, None] * P[tri]).sum(axis=1)

@@ -173,3 +173,42 @@ def test_render_kernel_keeps_its_top_k_in_registers(tmp_path):
     # the host wrapper refuses a launch that would ask for more than 64 KiB in all
     text = open(src).read()
     assert "RENDER_MAX_LDS = 64 * 1024" in text and "lds_verts + lds_static > (size_t)RENDER_MAX_LDS" in text
+
+
+def test_tie_mode_orders_equal_depths_by_face_index():
+    """12 congruent fronto-parallel triangles at Z = 1 (tests/raster_scenes.py): their depths are equal in exact arithmetic, and
+    bit-equal in the kernel.  The float64 restatement gives them two or three values one ulp (2.2e-16) apart, so its default order among them is
+    rounding noise; the tie mode (tie_rel) orders them by face index.  The default mode is unchanged."""
+    import raster_scenes as SC
+    v, f = SC.tie12()
+    K = SC.dyadic_K(64)[0]
+    SC.assert_exact_projection(v, K, 64)
+    SC.assert_tie_group(v, f, K, 64, np.arange(12))
+    pix, face, pz, dist, wmin, ins = R.candidates(v, f, K, 64, blur_radius=SC.BLUR)
+    spread = pz.max() - pz.min()
+    print(f"distinct depths {np.unique(pz).size}, spread {spread:.3e}")
+    assert 2 <= np.unique(pz).size <= 3 and 2.2e-16 <= spread <= 4.5e-16      # equal depths, told apart by the last bit (1 ulp = 2.2e-16)
+    kw = dict(sigma=SC.SIGMA, blur_radius=SC.BLUR)
+    tie, plain = R.render(v, f, K, 64, tie_rel=SC.TIE_REL, **kw), R.render(v, f, K, 64, **kw)
+    full = tie["n_cand"] == 12
+    assert int((tie["n_cand"] > 10).sum()) == 466 and full.sum() > 300
+    assert (tie["top"][full] == np.arange(10)).all()                          # faces 0..9, in that order
+    assert (tie["tie_gap"] == np.inf).all() and (tie["z_gap"] == np.inf).all()    # one depth group: nothing is decided by a gap
+    assert (plain["top"][full] != np.arange(10)).any()                        # the default order follows the rounding
+    assert (plain["tie_gap"][full] <= 4.5e-16).all()
+    assert np.abs(plain["mask"] - tie["mask"]).max() > 1e-3                   # and blends other faces
+    assert tie["win_wmin"].min() == pytest.approx(0.0208, abs=1e-4)           # no winner near an edge
+    # face_idx: the lowest containing index, whatever the face order
+    v2, f2 = SC.tie12(rev=True)
+    rev = R.render(v2, f2, K, 64, tie_rel=SC.TIE_REL, **kw)
+    tri = lambda r, flip: np.where(r["face_idx"] >= 0, 11 - r["face_idx"] if flip else r["face_idx"], -1)
+    covered = tie["face_idx"] >= 0
+    assert (tri(rev, True)[covered] >= tri(tie, False)[covered]).all() and (tri(rev, True) != tri(tie, False)).any()
+    # distinct depths: the tie mode changes nothing (the existing scenes' reference stays what it was)
+    S = 16
+    K16 = _K(S)
+    verts = np.array([_unproject(*p, 0.9 - 0.05 * k, K16) for k in range(12) for p in ((3, 3), (12, 3), (3, 12))])
+    faces = np.arange(36).reshape(12, 3)
+    a, b = R.render(verts, faces, K16, S), R.render(verts, faces, K16, S, tie_rel=SC.TIE_REL)
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert "top" in a and a["top"][5, 5].tolist() == list(range(11, 1, -1))

@@ -168,3 +168,44 @@ def test_background_is_floored_to_eight_bits():
     x = torch.from_numpy(rng.rand(2, 3, 4, 4).astype(np.float32))
     mean, std = torch.tensor([0.485, 0.456, 0.406]).reshape(1, 3, 1, 1), torch.tensor([0.229, 0.224, 0.225]).reshape(1, 3, 1, 1)
     assert (hands_amd.denormalize_images((x - mean) / std) - x).abs().max() < 1e-6
+
+
+def test_tie_mode_keeps_equal_depths_with_the_lower_mesh_and_takes_the_callers_table():
+    """The same fronto-parallel triangle in three meshes (tests/raster_scenes.py): the tie mode gives every covered pixel to the
+    first valid mesh and reports no unsure pixel; the default mode calls the same pixels unsure (gap 0 or rounding).  A mesh may
+    carry the caller's CSR table: an empty one gives zero normals, i.e. the n = v fallback."""
+    import raster_scenes as SC
+    K = SC.dyadic_K(64)[0]
+    meshes = [dict(verts=v, faces=f, color=SC.COLORS[m], valid=m > 0) for m, (v, f) in enumerate(SC.same_triangle_meshes(3))]
+    for M in meshes:
+        SC.assert_exact_projection(M["verts"], K, 64)
+        SC.assert_tie_group(M["verts"], M["faces"], K, 64, np.arange(2))
+    tie, plain = R.render(meshes, K, 64, tie_rel=SC.TIE_REL), R.render(meshes, K, 64)
+    cov = tie["covered"]
+    assert cov.sum() == 192 and (tie["face_id"][cov] == 2).all()              # mesh 0 is off: (mesh 1, face 0) = 2 + 0
+    assert not tie["unsure"].any() and (tie["gap"][cov] == np.inf).all()
+    assert plain["unsure"][cov].all() and (plain["gap"][cov] < 1e-12).all()   # the default cannot judge these pixels
+    want = R.render(meshes[1:2], K, 64)
+    assert np.array_equal(tie["rgb"], want["rgb"]) and np.array_equal(tie["depth"], want["depth"])
+    # distinct depths: the tie mode changes nothing
+    verts, faces = R.uv_sphere(6, 8, 0.045, (0.013, -0.007, 0.40))
+    Ks = np.array([[165.0, 0, 22], [0, 165.0, 22], [0, 0, 1]])
+    one = [dict(verts=verts, faces=faces, color=(0.2, 0.5, 0.7))]
+    a, b = R.render(one, Ks, 44), R.render(one, Ks, 44, tie_rel=SC.TIE_REL)
+    assert a["covered"].sum() > 100 and all(np.array_equal(a[k], b[k]) for k in a)
+    # the caller's table
+    from hands_amd.rend_utils import build_vertex_face_csr
+    P = verts.astype(np.float64)
+    off, ids = build_vertex_face_csr(faces, verts.shape[0])
+    assert np.abs(R.vertex_normals_csr(P, faces, off, ids) - R.vertex_normals(P, faces)).max() < 1e-15
+    junk = np.concatenate([[-1, faces.shape[0]], ids]).astype(np.int32)        # entries out of range add nothing
+    assert np.array_equal(R.vertex_normals_csr(P, faces, off + 2 * (np.arange(off.size) > 0), junk),
+                          R.vertex_normals_csr(P, faces, off, ids))
+    empty = (np.zeros(verts.shape[0] + 1, np.int32), np.zeros(0, np.int32))
+    assert (R.vertex_normals_csr(P, faces, *empty) == 0).all()
+    c = R.render([dict(one[0], csr=empty)], Ks, 44)
+    assert np.array_equal(c["face_id"], a["face_id"]) and np.abs(c["rgb"] - a["rgb"]).max() > 0.01
+    centre = np.unravel_index(np.argmin(np.where(a["covered"], a["depth"], np.inf)), a["depth"].shape)
+    assert np.abs(c["rgb"][centre] - a["rgb"][centre]).max() < 0.02           # n = v is the true normal where the sphere faces the eye
+    d = R.render([dict(one[0], n_draw=10)], Ks, 44)
+    assert 0 < d["covered"].sum() < a["covered"].sum() and d["face_id"].max() < 10
