@@ -53,6 +53,27 @@ class EvalOut(C.Structure):
         "mpjpe_ra_h", "mpjpe_pa_ra_r", "mpjpe_pa_ra_l", "mpjpe_pa_ra_h", "mrrpe_rl", "pix_err_r", "pix_err_l")]
 
 
+class EvalMaskedOut(C.Structure):
+    """hands_eval_masked_out (include/hands_hip.h): the nine values of the egoexo branch of eval_mpjpe_pa_ra."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "rao_r", "rao_l", "rao_h", "abs_r", "abs_l", "abs_h", "pa_ra_r", "pa_ra_l", "pa_ra_h")]
+
+
+class MeshEvalIn(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in (
+        "pred_v3d_r", "pred_v3d_l", "gt_v3d_r", "gt_v3d_l", "pred_j3d_r", "pred_j3d_l", "gt_j3d_r", "gt_j3d_l",
+        "is_valid", "right_valid", "left_valid")]
+
+
+MESH_MAX_V, MESH_NQ = 1024, 10            # HANDS_MESH_MAX_V, HANDS_MESH_NQ
+# hands_mesh_eval_out: quantity q of hand s (r, l, h) is pointer 3 * q + s
+MESH_QUANTITIES = ("mpvpe_ra", "f5_ra", "f15_ra", "auc_ra_v", "auc_ra_j", "mpvpe_pa", "f5_pa", "f15_pa", "auc_pa_v", "auc_pa_j")
+
+
+class MeshEvalOut(C.Structure):
+    _fields_ = [(f"{q}_{s}", C.c_void_p) for q in MESH_QUANTITIES for s in "rlh"]
+
+
 class LossIn(C.Structure):
     """hands_loss_in (include/hands_hip.h): the first LOSS_N_MANDATORY pointers are mandatory, the rest come in groups."""
     _fields_ = [(n, C.c_void_p) for n in (
@@ -158,6 +179,8 @@ SIGNATURES = {
     "hands_flash_attention_f32": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     "hands_ceiling_hbm_read_f32": [_P, C.c_longlong, _P, _P],
     "hands_eval_metrics_f32": [C.POINTER(EvalIn), C.POINTER(EvalOut), _I, _P],
+    "hands_eval_metrics_masked_f32": [C.POINTER(EvalIn), _P, _P, C.POINTER(EvalMaskedOut), _I, _P],
+    "hands_eval_mesh_metrics_f32": [C.POINTER(MeshEvalIn), C.POINTER(MeshEvalOut), _I, _I, _P],
     "hands_loss_light_f32": [C.POINTER(LossIn), _I, _I, _I, _P, _P, _P, _P, _P],
     "hands_mano_pose_aa_f32": [C.POINTER(ManoConsts), _P, _P, _I, _P, _I, _P, _P, _I, _P],
     "hands_gt_targets_f32": [_P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _P],

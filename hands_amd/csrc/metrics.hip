@@ -1,7 +1,9 @@
 // metrics.hip -- evaluation metrics on device for the gathered predictions:
 // root-aligned MPJPE, Procrustes-aligned MPJPE (3x3 SVD per hand), hand-to-hand MRRPE, 2-D pixel error.
 // Reference: src/utils/eval_modules.py:97-134,136-219,320-343,386-428; common/metrics.py:23-55;
-// common/torch_utils.py:14-19 (nanmean).  One thread per sample; the work is ~2 kFLOP per hand.
+// common/torch_utils.py:14-19 (nanmean).  One thread per sample; the work is ~2 kFLOP per hand.  eval_metrics_masked_kernel is
+// the other branch of eval_mpjpe_pa_ra (:231-317): only the flagged joints of a hand, rooted at the first of them.
+// The 3x3 solve behind every alignment is procrustes_solve (procrustes_device.h), shared with mesh_metrics.hip.
 // Rank-deficient Procrustes: the rotation is V diag(1,1,det V) U^T with U an orthonormal frame whatever the rank of the
 // cross-covariance K.  Rank 2 (planar joints): U_2 = U_0 x U_1.  Rank 1 (the predicted or the ground-truth joints on a line):
 // U_1 is completed from the unit axis least aligned with U_0; the error does not depend on the completion and equals the one
@@ -11,6 +13,7 @@
 #include <stdint.h>
 #include "hands_hip.h"
 #include "common.h"
+#include "procrustes_device.h"
 
 namespace {
 
@@ -30,111 +33,91 @@ __device__ float mpjpe_ra(const float* gt, const float* pr) {
   return s / (float)NJ;
 }
 
-// symmetric 3x3 eigen-decomposition by cyclic Jacobi (fp64): A = V diag(w) V^T
-__device__ void jacobi3(double A[3][3], double V[3][3], double w[3]) {
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 12; ++sweep) {
-    const double off = fabs(A[0][1]) + fabs(A[0][2]) + fabs(A[1][2]);
-    if (off < 1e-300) break;
-    for (int p = 0; p < 2; ++p)
-      for (int q = p + 1; q < 3; ++q) {
-        if (fabs(A[p][q]) < 1e-300) continue;
-        const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-        for (int k = 0; k < 3; ++k) {           // A <- A J
-          const double akp = A[k][p], akq = A[k][q];
-          A[k][p] = c * akp - s * akq; A[k][q] = s * akp + c * akq;
-        }
-        for (int k = 0; k < 3; ++k) {           // A <- J^T A
-          const double apk = A[p][k], aqk = A[q][k];
-          A[p][k] = c * apk - s * aqk; A[q][k] = s * apk + c * aqk;
-        }
-        for (int k = 0; k < 3; ++k) {
-          const double vkp = V[k][p], vkq = V[k][q];
-          V[k][p] = c * vkp - s * vkq; V[k][q] = s * vkp + c * vkq;
-        }
-      }
+// compute_similarity_transform of a 2 x 3 array: the reference transposes its (n,3) input unless n is 2 or 3
+// (eval_modules.py:144), so two selected joints are read as THREE points in the plane, point k = (S[0][k], S[1][k]), and the
+// error is taken along the rows of the 2 x 3 result (:216).  The proper rotation maximising trace(R K) in the plane is closed
+// form: trace(R K) = cos(th) (K00 + K11) + sin(th) (K01 - K10).
+__device__ float pa_error_2x3(const double S1[][3], const double S2[][3]) {
+  double mu1[2], mu2[2], K[2][2] = {{0, 0}, {0, 0}}, var1 = 0;
+  for (int a = 0; a < 2; ++a) {
+    mu1[a] = ((S1[a][0] + S1[a][1]) + S1[a][2]) / 3.0;
+    mu2[a] = ((S2[a][0] + S2[a][1]) + S2[a][2]) / 3.0;
   }
-  for (int i = 0; i < 3; ++i) w[i] = A[i][i];
+  for (int k = 0; k < 3; ++k)
+    for (int a = 0; a < 2; ++a) {
+      const double x1 = S1[a][k] - mu1[a];
+      var1 += x1 * x1;
+      for (int b = 0; b < 2; ++b) K[a][b] += x1 * (S2[b][k] - mu2[b]);
+    }
+  const double c0 = K[0][0] + K[1][1], s0 = K[0][1] - K[1][0], tr = sqrt(c0 * c0 + s0 * s0);
+  const double c = tr > 0 ? c0 / tr : 1.0, sn = tr > 0 ? s0 / tr : 0.0;      // tr = 0: the scale is 0 (or NaN), any rotation
+  const double R[2][2] = {{c, -sn}, {sn, c}};
+  const double scale = tr / var1;
+  double s = 0;
+  for (int a = 0; a < 2; ++a) {
+    const double t = mu2[a] - scale * (R[a][0] * mu1[0] + R[a][1] * mu1[1]);
+    double d2 = 0;
+    for (int k = 0; k < 3; ++k) {
+      const double h = scale * (R[a][0] * S1[0][k] + R[a][1] * S1[1][k]) + t;
+      d2 += (S2[a][k] - h) * (S2[a][k] - h);
+    }
+    s += sqrt(d2);
+  }
+  return (float)(s / 2.0);
 }
 
-// Procrustes-aligned mean joint error of ROOT-ALIGNED joints (eval_modules.py:136-219)
-__device__ float mpjpe_pa(const float* gt, const float* pr) {
+// Procrustes-aligned mean error of ROOT-ALIGNED joints (eval_modules.py:136-219) over the n <= 21 joints sel[0..n) (all 21 in
+// order when sel is null), root = the first of them.  n = 2 and n = 3 follow the reference's reading of a 2 x 3 / 3 x 3
+// array (see pa_error_2x3): for n = 3 the COLUMNS are the points and the error is taken along the rows.
+__device__ float mpjpe_pa_sel(const float* gt, const float* pr, const int* sel, int n) {
   double S1[NJ][3], S2[NJ][3], mu1[3] = {0, 0, 0}, mu2[3] = {0, 0, 0};
-  for (int j = 0; j < NJ; ++j)
-    for (int c = 0; c < 3; ++c) {
-      S1[j][c] = (double)(pr[3 * j + c] - pr[c]);      // root alignment in fp32, as the reference
-      S2[j][c] = (double)(gt[3 * j + c] - gt[c]);
-      mu1[c] += S1[j][c]; mu2[c] += S2[j][c];
+  const int root = sel ? sel[0] : 0;
+  if (n == 2 || n == 3) {
+    double T1[3][3], T2[3][3];
+    for (int j = 0; j < n; ++j)
+      for (int c = 0; c < 3; ++c) {
+        T1[j][c] = (double)(pr[3 * sel[j] + c] - pr[3 * root + c]);
+        T2[j][c] = (double)(gt[3 * sel[j] + c] - gt[3 * root + c]);
+      }
+    if (n == 2) return pa_error_2x3(T1, T2);
+    for (int j = 0; j < 3; ++j)                          // point j = column j
+      for (int c = 0; c < 3; ++c) {
+        S1[j][c] = T1[c][j]; S2[j][c] = T2[c][j];
+        mu1[c] += S1[j][c]; mu2[c] += S2[j][c];
+      }
+  } else {
+    for (int j = 0; j < n; ++j) {
+      const int js = sel ? sel[j] : j;
+      for (int c = 0; c < 3; ++c) {
+        S1[j][c] = (double)(pr[3 * js + c] - pr[3 * root + c]);      // root alignment in fp32, as the reference
+        S2[j][c] = (double)(gt[3 * js + c] - gt[3 * root + c]);
+        mu1[c] += S1[j][c]; mu2[c] += S2[j][c];
+      }
     }
-  for (int c = 0; c < 3; ++c) { mu1[c] /= NJ; mu2[c] /= NJ; }
+  }
+  for (int c = 0; c < 3; ++c) { mu1[c] /= n; mu2[c] /= n; }
   double K[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, var1 = 0;
-  for (int j = 0; j < NJ; ++j)
+  for (int j = 0; j < n; ++j)
     for (int a = 0; a < 3; ++a) {
       const double x1 = S1[j][a] - mu1[a];
       var1 += x1 * x1;
       for (int b = 0; b < 3; ++b) K[a][b] += x1 * (S2[j][b] - mu2[b]);
     }
-  // K = U S V^T; eigen-decompose K^T K = V S^2 V^T
-  double A[3][3], V[3][3], w[3];
-  for (int a = 0; a < 3; ++a)
-    for (int b = 0; b < 3; ++b) A[a][b] = K[0][a] * K[0][b] + K[1][a] * K[1][b] + K[2][a] * K[2][b];
-  jacobi3(A, V, w);
-  int o[3] = {0, 1, 2};                                  // sort singular values descending
-  for (int i = 0; i < 2; ++i)
-    for (int j = i + 1; j < 3; ++j)
-      if (w[o[j]] > w[o[i]]) { const int t = o[i]; o[i] = o[j]; o[j] = t; }
-  double Vs[3][3], U[3][3];
-  for (int i = 0; i < 3; ++i)
-    for (int r = 0; r < 3; ++r) Vs[r][i] = V[r][o[i]];
-  // U is an orthonormal frame whatever the rank of K.  U_0 = K V_0 / |K V_0| (e_x when K = 0: scale is 0 or NaN then and the
-  // frame does not matter).  U_1 = K V_1 made orthogonal to U_0; when what is left is below 1e-10 |K V_0| -- K has rank 1: the
-  // predicted or the ground-truth joints lie on a line, and K V_1 is zero or rounding noise parallel to U_0 -- the unit axis
-  // least aligned with U_0 takes its place.  Any orthonormal completion gives the same error there, as for LAPACK's.
-  double u0[3], u1[3], n0 = 0;
-  for (int r = 0; r < 3; ++r) {
-    u0[r] = K[r][0] * Vs[0][0] + K[r][1] * Vs[1][0] + K[r][2] * Vs[2][0];
-    u1[r] = K[r][0] * Vs[0][1] + K[r][1] * Vs[1][1] + K[r][2] * Vs[2][1];
-    n0 += u0[r] * u0[r];
-  }
-  n0 = sqrt(n0);
-  for (int r = 0; r < 3; ++r) U[r][0] = n0 > 0 ? u0[r] / n0 : (r == 0 ? 1.0 : 0.0);
-  for (int pass = 0; pass < 2; ++pass) {
-    double n1 = 0;
-    for (int again = 0; again < 2; ++again) {            // Gram-Schmidt twice: the first pass may cancel almost everything
-      const double d = u1[0] * U[0][0] + u1[1] * U[1][0] + u1[2] * U[2][0];
-      for (int r = 0; r < 3; ++r) u1[r] -= d * U[r][0];
-    }
-    for (int r = 0; r < 3; ++r) n1 += u1[r] * u1[r];
-    n1 = sqrt(n1);
-    if (pass == 1 || (n0 > 0 && n1 > 1e-10 * n0)) {
-      for (int r = 0; r < 3; ++r) U[r][1] = u1[r] / n1;
-      break;
-    }
-    int ax = 0;
-    for (int r = 1; r < 3; ++r)
-      if (fabs(U[r][0]) < fabs(U[ax][0])) ax = r;
-    for (int r = 0; r < 3; ++r) u1[r] = r == ax ? 1.0 : 0.0;
-  }
-  U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1];      // U_3 = U_1 x U_2  (det U = +1)
-  U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1];
-  U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];
-  const double detV = Vs[0][0] * (Vs[1][1] * Vs[2][2] - Vs[1][2] * Vs[2][1]) -
-                      Vs[0][1] * (Vs[1][0] * Vs[2][2] - Vs[1][2] * Vs[2][0]) +
-                      Vs[0][2] * (Vs[1][0] * Vs[2][1] - Vs[1][1] * Vs[2][0]);
-  const double z = detV >= 0 ? 1.0 : -1.0;               // R = V diag(1,1,det V) U^T maximises trace(R K)
-  double R[3][3], tr = 0;
-  for (int a = 0; a < 3; ++a)
-    for (int b = 0; b < 3; ++b) R[a][b] = Vs[a][0] * U[b][0] + Vs[a][1] * U[b][1] + z * Vs[a][2] * U[b][2];
-  for (int a = 0; a < 3; ++a)
-    for (int b = 0; b < 3; ++b) tr += R[a][b] * K[b][a];
-  const double scale = tr / var1;
+  double R[3][3], scale;
+  procrustes_solve(K, var1, R, &scale);
   double t[3];
   for (int a = 0; a < 3; ++a) t[a] = mu2[a] - scale * (R[a][0] * mu1[0] + R[a][1] * mu1[1] + R[a][2] * mu1[2]);
+  if (n == 3) {                                          // error along the rows of the 3 x 3 result: one per coordinate
+    double d2[3] = {0, 0, 0};
+    for (int j = 0; j < 3; ++j)
+      for (int a = 0; a < 3; ++a) {
+        const double h = scale * (R[a][0] * S1[j][0] + R[a][1] * S1[j][1] + R[a][2] * S1[j][2]) + t[a];
+        d2[a] += (S2[j][a] - h) * (S2[j][a] - h);
+      }
+    return (float)(((sqrt(d2[0]) + sqrt(d2[1])) + sqrt(d2[2])) / 3.0);
+  }
   double s = 0;
-  for (int j = 0; j < NJ; ++j) {
+  for (int j = 0; j < n; ++j) {
     double d2 = 0;
     for (int a = 0; a < 3; ++a) {
       const double h = scale * (R[a][0] * S1[j][0] + R[a][1] * S1[j][1] + R[a][2] * S1[j][2]) + t[a];
@@ -142,8 +125,10 @@ __device__ float mpjpe_pa(const float* gt, const float* pr) {
     }
     s += sqrt(d2);
   }
-  return (float)(s / NJ);
+  return (float)(s / n);
 }
+
+__device__ float mpjpe_pa(const float* gt, const float* pr) { return mpjpe_pa_sel(gt, pr, nullptr, NJ); }
 
 __device__ __forceinline__ float nanmean2(float a, float b) {
   const bool na = isnan(a), nb = isnan(b);
@@ -180,6 +165,48 @@ __global__ void eval_metrics_kernel(hands_eval_in in, hands_eval_out out, int B)
     out.pix_err_r[i] = in.joints_valid_r[i] * rv != 0.f ? sqrtf(dxr * dxr + dyr * dyr) : NaN;
     out.pix_err_l[i] = in.joints_valid_l[i] * lv != 0.f ? sqrtf(dxl * dxl + dyl * dyl) : NaN;
   }
+}
+
+// The egoexo branch of eval_mpjpe_pa_ra (eval_modules.py:231-317) for one hand: only the joints flagged in jv3d (21) count,
+// the root is the first of them.  None flagged: all three NaN.  The PA error is multiplied by the hand's validity (:217).
+__device__ void masked_hand(const float* gt, const float* pr, const float* jv3d, float valid, float* rao, float* abs_, float* pa) {
+  int sel[NJ], n = 0;
+  for (int j = 0; j < NJ; ++j)
+    if (jv3d[j] != 0.f) sel[n++] = j;                   // .bool(): any non-zero flag (a NaN flag included)
+  if (n == 0) {
+    *rao = *abs_ = *pa = __builtin_nanf("");
+    return;
+  }
+  float sa = 0.f, sr = 0.f;
+  for (int k = 0; k < n; ++k) {
+    float a2 = 0.f, r2 = 0.f;
+    for (int c = 0; c < 3; ++c) {
+      const float g = gt[3 * sel[k] + c], p = pr[3 * sel[k] + c];
+      const float da = g - p, dr = (g - gt[3 * sel[0] + c]) - (p - pr[3 * sel[0] + c]);
+      a2 += da * da;
+      r2 += dr * dr;
+    }
+    sa += sqrtf(a2);
+    sr += sqrtf(r2);
+  }
+  *abs_ = sa / (float)n;
+  *rao = sr / (float)n;
+  *pa = mpjpe_pa_sel(gt, pr, sel, n) * valid;
+}
+
+__global__ void eval_metrics_masked_kernel(hands_eval_in in, const float* __restrict__ jv3d_r, const float* __restrict__ jv3d_l,
+                                           hands_eval_masked_out out, int B) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const float isv = in.is_valid[b];
+  const float rv = in.right_valid[b] * isv, lv = in.left_valid[b] * isv;
+  const long long o = (long long)b * NJ;
+  float rao_r, abs_r, pa_r, rao_l, abs_l, pa_l;
+  masked_hand(in.gt_j3d_r + o * 3, in.pred_j3d_r + o * 3, jv3d_r + o, rv, &rao_r, &abs_r, &pa_r);
+  masked_hand(in.gt_j3d_l + o * 3, in.pred_j3d_l + o * 3, jv3d_l + o, lv, &rao_l, &abs_l, &pa_l);
+  out.rao_r[b] = rao_r * 1000.0f; out.rao_l[b] = rao_l * 1000.0f; out.rao_h[b] = nanmean2(rao_r, rao_l) * 1000.0f;
+  out.abs_r[b] = abs_r * 1000.0f; out.abs_l[b] = abs_l * 1000.0f; out.abs_h[b] = nanmean2(abs_r, abs_l) * 1000.0f;
+  out.pa_ra_r[b] = pa_r * 1000.0f; out.pa_ra_l[b] = pa_l * 1000.0f; out.pa_ra_h[b] = nanmean2(pa_r, pa_l) * 1000.0f;
 }
 
 // process_data_light (src/callbacks/process/process_arctic.py:41-73): camera-space targets from the
@@ -243,5 +270,19 @@ extern "C" int hands_eval_metrics_f32(const hands_eval_in* in, const hands_eval_
   for (size_t i = 0; i < sizeof(hands_eval_out) / sizeof(void*); ++i)
     if (!po[i]) return HANDS_EINVAL;
   hipLaunchKernelGGL(eval_metrics_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, *in, *out, B);
+  HANDS_LAUNCH_CHECK();
+}
+
+extern "C" int hands_eval_metrics_masked_f32(const hands_eval_in* in, const float* joints3d_valid_r, const float* joints3d_valid_l,
+                                             const hands_eval_masked_out* out, int B, hands_stream_t stream) {
+  if (!in || !out || !joints3d_valid_r || !joints3d_valid_l || B <= 0) return HANDS_EINVAL;
+  const void* const* pi = reinterpret_cast<const void* const*>(in);
+  for (size_t i = 0; i < sizeof(hands_eval_in) / sizeof(void*); ++i)
+    if (!pi[i]) return HANDS_EINVAL;
+  const void* const* po = reinterpret_cast<const void* const*>(out);
+  for (size_t i = 0; i < sizeof(hands_eval_masked_out) / sizeof(void*); ++i)
+    if (!po[i]) return HANDS_EINVAL;
+  hipLaunchKernelGGL(eval_metrics_masked_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, *in, joints3d_valid_r,
+                     joints3d_valid_l, *out, B);
   HANDS_LAUNCH_CHECK();
 }

@@ -4,7 +4,11 @@
 models -- ``eval_mpjpe_ra``, ``eval_mpjpe_pa_ra`` (21-joint branch), ``eval_mrrpe_hand``,
 ``eval_pixel_error`` (src/utils/eval_modules.py:97-134,221-343,386-428) -- with one kernel launch for
 the whole batch instead of a per-sample numpy loop with a LAPACK SVD per hand.  Same keys, same units
-(mm / px), same NaN conventions; tensors stay on the device.
+(mm / px), same NaN conventions; tensors stay on the device.  With ``'egoexo' in meta_info['dataset']`` the reference
+takes the other branch of ``eval_mpjpe_pa_ra`` (:231-317, joints flagged in ``joints3d_valid_{r,l}`` only) and so does this.
+
+``evaluate_mesh_metrics(pred, targets)`` adds what mesh papers report and the reference does not compute: MPVPE, F@5mm /
+F@15mm and the AUC of the PCK curve, root-aligned and Procrustes-aligned, for the 778 vertices of each hand.
 """
 from __future__ import annotations
 
@@ -13,8 +17,24 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import EvalIn, EvalOut, check, ptr
+from ._lib import EvalIn, EvalMaskedOut, EvalOut, MeshEvalIn, MeshEvalOut, check, ptr
 from .xdict import xdict
+
+# keys of evaluate_mesh_metrics without the hand suffix, in the order of hands_mesh_eval_out (_lib.MESH_QUANTITIES)
+MESH_KEYS = tuple(k.format(a) for a in ("ra", "pa")
+                  for k in ("mpvpe/{}", "fscore/{}/5", "fscore/{}/15", "auc/{}/v", "auc/{}/j"))
+MASKED_KEYS = ("mpjpe/pa/rao", "mpjpe/pa/abs", "mpjpe/pa/ra")
+
+
+def _is_egoexo(meta_info) -> bool:
+    """The reference's own test (src/utils/eval_modules.py:231): ``'egoexo' in meta_info['dataset']``."""
+    if meta_info is None:
+        return False
+    try:
+        dataset = meta_info["dataset"]
+    except KeyError:
+        return False
+    return "egoexo" in dataset
 
 
 def evaluate_metrics(pred: dict, targets: dict, meta_info: dict | None = None) -> xdict:
@@ -34,8 +54,41 @@ def evaluate_metrics(pred: dict, targets: dict, meta_info: dict | None = None) -
     ein = EvalIn(*[ptr(t) for t in keep])
     eout = EvalOut(ptr(o["mpjpe/ra/h"]), ptr(o["mpjpe/pa/ra/r"]), ptr(o["mpjpe/pa/ra/l"]), ptr(o["mpjpe/pa/ra/h"]),
                    ptr(o["mrrpe/r/l"]), ptr(o["pix_err/r"]), ptr(o["pix_err/l"]))
-    check(L.hands_eval_metrics_f32(C.byref(ein), C.byref(eout), B, torch.cuda.current_stream(dev).cuda_stream),
-          "hands_eval_metrics_f32")
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    check(L.hands_eval_metrics_f32(C.byref(ein), C.byref(eout), B, stream), "hands_eval_metrics_f32")
+    if _is_egoexo(meta_info):
+        # the other branch of eval_mpjpe_pa_ra (eval_modules.py:231-317): its nine keys replace the three mpjpe/pa/ra/*
+        jv3d = [f(targets["joints3d_valid_r"]), f(targets["joints3d_valid_l"])]
+        assert jv3d[0].shape == (B, 21) and jv3d[1].shape == (B, 21)
+        for k in MASKED_KEYS:
+            for s in "rlh":
+                o[f"{k}/{s}"] = torch.empty(B, device=dev)
+        mout = EvalMaskedOut(*[ptr(o[f"{k}/{s}"]) for k in MASKED_KEYS for s in "rlh"])
+        check(L.hands_eval_metrics_masked_f32(C.byref(ein), ptr(jv3d[0]), ptr(jv3d[1]), C.byref(mout), B, stream),
+              "hands_eval_metrics_masked_f32")
     out = xdict(o)
     out["pix_err/h"] = torch.cat((o["pix_err/r"], o["pix_err/l"]), dim=1)
     return out
+
+
+def evaluate_mesh_metrics(pred: dict, targets: dict, meta_info: dict | None = None) -> xdict:
+    """Mesh metrics of both hands in one launch (hands_eval_mesh_metrics_f32): ``mpvpe/{ra,pa}/*`` (mm),
+    ``fscore/{ra,pa}/{5,15}/*``, ``auc/{ra,pa}/{v,j}/*`` for ``* = r, l, h``, each a (B) tensor on the device of the inputs.
+    Needs ``mano.v3d.cam.{r,l}`` (B,V,3) and ``mano.j3d.cam.{r,l}`` (B,21,3) in ``pred`` and ``targets`` and
+    ``is_valid`` / ``right_valid`` / ``left_valid`` (B) in ``targets``.  Invalid hands are NaN, as ``mpjpe/ra``."""
+    dev = pred["mano.v3d.cam.r"].device
+    if dev.type != "cuda":
+        raise RuntimeError("hands_amd.evaluate_mesh_metrics runs on a HIP device only (no CPU fallback)")
+    L = _lib.lib()
+    f = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()
+    B, V = pred["mano.v3d.cam.r"].shape[:2]
+    keep = [f(pred["mano.v3d.cam.r"]), f(pred["mano.v3d.cam.l"]), f(targets["mano.v3d.cam.r"]), f(targets["mano.v3d.cam.l"]),
+            f(pred["mano.j3d.cam.r"]), f(pred["mano.j3d.cam.l"]), f(targets["mano.j3d.cam.r"]), f(targets["mano.j3d.cam.l"]),
+            f(targets["is_valid"]), f(targets["right_valid"]), f(targets["left_valid"])]
+    assert all(t.shape == (B, V, 3) for t in keep[:4]) and all(t.shape == (B, 21, 3) for t in keep[4:8])
+    assert all(t.shape == (B,) for t in keep[8:])
+    buf = torch.empty(len(MESH_KEYS) * 3, B, device=dev)
+    mout = MeshEvalOut(*[ptr(buf[i]) for i in range(buf.shape[0])])
+    check(L.hands_eval_mesh_metrics_f32(C.byref(MeshEvalIn(*[ptr(t) for t in keep])), C.byref(mout), B, V,
+                                        torch.cuda.current_stream(dev).cuda_stream), "hands_eval_mesh_metrics_f32")
+    return xdict({f"{k}/{s}": buf[3 * i + j] for i, k in enumerate(MESH_KEYS) for j, s in enumerate("rlh")})

@@ -35,6 +35,9 @@ class HandsWrapper(nn.Module):
         # the reference wrapper owns its own MANO layers for GT processing (generic/wrapper.py:36-39)
         self.mano_r = self.model.mano_r.mano
         self.mano_l = self.model.mano_l.mano
+        # generic/wrapper.py:44-54.  The four reference names are always evaluated (one launch gives them all); the extra
+        # name "mesh" adds evaluate_mesh_metrics' MPVPE / F-score / AUC keys to what forward(..., "test") returns
+        self.metric_dict = ["mrrpe.rl", "mpjpe.ra", "mpjpe.pa.ra", "pix_err"]
 
     def inference_pose(self, inputs, meta_info):
         pred = self.model(inputs, meta_info)
@@ -138,8 +141,10 @@ class HandsWrapper(nn.Module):
                                 **meta_info.prefix("meta_info.")}).detach()
         if mode == "vis":
             return merged()
-        from .metrics import evaluate_metrics
+        from .metrics import evaluate_mesh_metrics, evaluate_metrics
         metrics_all = evaluate_metrics(pred, targets, meta_info).detach()
+        if "mesh" in self.metric_dict:
+            metrics_all.merge(evaluate_mesh_metrics(pred, targets, meta_info).detach())
         out_dict = xdict()
         out_dict["imgname"] = meta_info.get("imgname")
         out_dict.merge({"metric." + k: v for k, v in metrics_all.items()})

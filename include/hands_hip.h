@@ -602,6 +602,62 @@ typedef struct hands_eval_out {
 int hands_eval_metrics_f32(const hands_eval_in* in, const hands_eval_out* out, int B,
                            hands_stream_t stream);
 
+/* The other branch of eval_mpjpe_pa_ra, taken when 'egoexo' is in meta_info['dataset'] (src/utils/eval_modules.py:231-317):
+ * per hand only the joints flagged in joints3d_valid_{r,l} (B,21; any non-zero value flags) are scored.  abs = mean
+ * camera-space error, rao = mean error after subtracting the FIRST flagged joint, pa_ra = Procrustes error of that
+ * root-aligned subset times hand_valid * is_valid (an invalid hand gives 0, not NaN, :217).  No joint flagged: NaN in all
+ * three; one joint flagged: rao 0 and pa_ra NaN (scale 0 / 0, as the reference).  Two or three joints flagged: the reference's
+ * compute_similarity_transform transposes its (n,3) input unless n is 2 or 3 (:144), so two joints are aligned as THREE points
+ * in the plane and three joints as the three COLUMNS of the 3 x 3 array, the error running along the rows of the result; this
+ * entry does the same.  h = nanmean of r and l.  Millimetres.
+ * `in` is the struct of hands_eval_metrics_f32, every pointer of it mandatory (the 2-D ones are not read).
+ * HANDS_EINVAL (nothing launched): a NULL pointer, B <= 0. */
+typedef struct hands_eval_masked_out {
+  float *rao_r, *rao_l, *rao_h, *abs_r, *abs_l, *abs_h, *pa_ra_r, *pa_ra_l, *pa_ra_h; /* (B) each */
+} hands_eval_masked_out;
+
+int hands_eval_metrics_masked_f32(const hands_eval_in* in, const float* joints3d_valid_r, const float* joints3d_valid_l,
+                                  const hands_eval_masked_out* out, int B, hands_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Mesh metrics on device (csrc/mesh_metrics.hip), one launch per batch, no allocation, no host synchronisation, no atomics:
+ * bit-reproducible from run to run and independent of the batch a sample sits in.  Replaces the host loop a user writes over
+ * mano.v3d.cam.* (a V x V nearest-neighbour search per hand in numpy); the F-score is the FreiHAND evaluation's
+ * calculate_fscore, the AUC its PCK curve, the alignment compute_similarity_transform of src/utils/eval_modules.py:136-187.
+ *
+ * Inputs fp32: vertices (B,V,3) with 1 <= V <= HANDS_MESH_MAX_V, joints (B,21,3), flags (B).  Per hand, two alignments:
+ *   ra  the root joint j3d[:,0] is subtracted from joints and vertices, pred from pred and gt from gt, in fp32;
+ *   pa  the similarity transform fitted (fp64) on the root-aligned V vertices -- for auc_*_j on the 21 joints, the alignment
+ *       of mpjpe/pa/ra -- is applied to the root-aligned prediction.  Rank-deficient clouds as hands_eval_metrics_f32.
+ * Outputs (B) each, HANDS_MESH_NQ quantities x {r, l, h}, h = nanmean of r and l:
+ *   mpvpe    mean over vertices of |gt_v - pred_v|, millimetres;
+ *   f5, f15  F = 2PR / (P + R), 0 when P + R = 0, with P = mean_i(min_j |gt_i - pred_j| < th), R = mean_j(min_i |pred_j - gt_i|
+ *            < th), th = 0.005 m / 0.015 m, strict <;
+ *   auc_v, auc_j  area under the PCK curve (fraction of vertices / joints with error <= t_k, t_k = k * 0.05 / 99 m,
+ *            k = 0..99), trapezoid rule, divided by 0.05.
+ * A hand with hand_valid * is_valid == 0 gives NaN in every output and its coordinates are not read; a valid hand with any
+ * non-finite vertex or joint coordinate gives NaN in every output of that hand.  A constant prediction gives NaN in the pa
+ * outputs, a constant ground truth mpvpe_pa 0.
+ * HANDS_EINVAL (nothing launched): a NULL pointer, B <= 0, V outside [1, HANDS_MESH_MAX_V].
+ * --------------------------------------------------------------------------------------------- */
+#define HANDS_MESH_MAX_V 1024
+#define HANDS_MESH_NQ 10
+typedef struct hands_mesh_eval_in {
+  const float *pred_v3d_r, *pred_v3d_l, *gt_v3d_r, *gt_v3d_l; /* (B,V,3) */
+  const float *pred_j3d_r, *pred_j3d_l, *gt_j3d_r, *gt_j3d_l; /* (B,21,3) */
+  const float *is_valid, *right_valid, *left_valid;           /* (B) */
+} hands_mesh_eval_in;
+
+typedef struct hands_mesh_eval_out { /* (B) each; quantity q, hand s (r, l, h) is pointer 3 * q + s of the struct */
+  float *mpvpe_ra_r, *mpvpe_ra_l, *mpvpe_ra_h, *f5_ra_r, *f5_ra_l, *f5_ra_h, *f15_ra_r, *f15_ra_l, *f15_ra_h;
+  float *auc_ra_v_r, *auc_ra_v_l, *auc_ra_v_h, *auc_ra_j_r, *auc_ra_j_l, *auc_ra_j_h;
+  float *mpvpe_pa_r, *mpvpe_pa_l, *mpvpe_pa_h, *f5_pa_r, *f5_pa_l, *f5_pa_h, *f15_pa_r, *f15_pa_l, *f15_pa_h;
+  float *auc_pa_v_r, *auc_pa_v_l, *auc_pa_v_h, *auc_pa_j_r, *auc_pa_j_l, *auc_pa_j_h;
+} hands_mesh_eval_out;
+
+int hands_eval_mesh_metrics_f32(const hands_mesh_eval_in* in, const hands_mesh_eval_out* out, int B, int V,
+                                hands_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * The validation loss dict on device, forward only (csrc/loss.hip): compute_loss_light of
  * src/callbacks/loss/loss_arctic_sf.py:20-206 (vector_loss / joints_loss / grasp_loss / render_loss of
