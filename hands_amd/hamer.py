@@ -15,14 +15,13 @@ same ``forward(inputs, meta_info) -> xdict`` contract, the same 22 output keys a
     vit.py:338, model.py:102-104 last_norm + kpe      hands_layernorm_f32 (fused add)
     mano_head.py:58-112 decoder, 6 layers             LN, GEMMs, hands_cross_attention_1q_f32
     geometry.py:47-62 rot6d (columns)                 hands_rot6d_to_matrix_cols_f32
-    model.py:125-139 MANOHead x2, grasp MLP           shared with hands_light
+    model.py:125-139 MANOHead x2, grasp MLP           hands_amd.mano_head; the same kernels as hands_light
 
 The single decoder token attends only to itself in the self-attention (softmax over one key is
 exactly 1), so that sub-layer is ``to_out(W_v LN(x)) + x`` -- bit-identical, two GEMMs.
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 
 import numpy as np
@@ -32,10 +31,12 @@ import torch.nn as nn
 from . import _lib
 from ._lib import ACT_GELU, ACT_NONE, ACT_RELU, check, ptr
 from .engine import ConvEngine, EngineSwitches
-from .hands_light import MANOHead, _Args, mano_consts, run_mano_heads
-from .packing import pack_conv, pack_linear, pack_mano
+from .mano_head import MANOHead, pack_mano_pair, run_mano_heads
+from .packing import hmr_decoder_rows, pack_conv, pack_linear
+from .streams import SideJobs
+from .vit_encoder import vit_encoder_blocks
 from .weights import synthetic_mano_mean_params
-from .xdict import xdict
+from .xdict import _Args, args_getter, xdict
 
 VIT_DIM, VIT_DEPTH, VIT_HEADS, VIT_HDIM = 1280, 32, 16, 80
 DEC_DIM, DEC_DEPTH, DEC_HEADS, DEC_HDIM = 1024, 6, 8, 64
@@ -183,7 +184,7 @@ class HAMER(EngineSwitches, nn.Module):
     def __init__(self, args=None, focal_length=1000.0, img_res=224, mano_assets=None, mean_params=None):
         super().__init__()
         args = args if args is not None else HAMER_DEFAULT_ARGS
-        get = args.get if hasattr(args, "get") else (lambda k, d=None: getattr(args, k, d))
+        get = args_getter(args)
         self.args = args
         # built: pos_enc 'center+corner_latent' (shipped) or None (no KPE: model.py:91-97,102-104), grasp head on or off
         # (model.py:59-72,136-143).  'dense_latent' cannot run in the reference either: PositionalEncoding.forward calls
@@ -274,8 +275,7 @@ class HAMER(EngineSwitches, nn.Module):
         mh = self.mano_head
         wd = torch.cat([cpu(mh.decpose.weight), cpu(mh.decshape.weight), cpu(mh.deccam.weight)], 0)
         bd = torch.cat([cpu(mh.decpose.bias), cpu(mh.decshape.bias), cpu(mh.deccam.bias)], 0)
-        rows = list(range(96)) + [96 + i for i in range(10)] + [108 + i for i in range(3)]
-        P["decout"] = pack_linear(wd, bd, dev, row_index=rows, n_total=112)
+        P["decout"] = pack_linear(wd, bd, dev, row_index=hmr_decoder_rows(), n_total=112)
         init = torch.zeros(112)
         init[:96], init[96:106], init[108:111] = cpu(mh.init_hand_pose)[0], cpu(mh.init_betas)[0], cpu(mh.init_cam)[0]
         P["init"] = init.to(dev)
@@ -285,10 +285,7 @@ class HAMER(EngineSwitches, nn.Module):
             P["g0"] = pack_linear(cpu(g[0].weight), cpu(g[0].bias), dev, col_index=gcol, k_total=154)
             P["g2"], P["g4"] = lin(g[2]), lin(g[4])
             P["g6"] = lin(g[6], n_total=12)
-        for side, head in (("mano_r", self.mano_r), ("mano_l", self.mano_l)):
-            m = pack_mano(head.mano.asset(), dev)
-            m["consts"] = mano_consts(m)
-            P[side] = m
+        P["mano_r"], P["mano_l"] = pack_mano_pair(self.mano_r, self.mano_l, dev)
         return P
 
     def packed(self, dev):
@@ -372,14 +369,7 @@ class HAMER(EngineSwitches, nn.Module):
             assert (ho, wo) == (TOKENS_H, TOKENS_W)
             check(L.hands_add_pos_f32(ptr(x), ptr(P["pos"]), ptr(kpe, lo * Cd) if kpe is not None else None, nB, T, Cd, sh), "add_pos")
             y, qkv, att, hid = cbuf("vit_y", Mc * Cd), cbuf("vit_qkv", Mc * 3 * Cd), cbuf("vit_att", Mc * Cd), cbuf("vit_h", Mc * 4 * Cd)
-            for blk in P["blocks"]:
-                lnorm(x, blk["n1"], y, Mc, Cd, 1e-6)
-                gemm(blk["qkv"], y, Mc, qkv)
-                check(L.hands_attention_f32(ptr(qkv), ptr(att), nB, T, VIT_HEADS, VIT_HDIM, scale, sh), "attention")
-                gemm(blk["proj"], att, Mc, x, res=x)
-                lnorm(x, blk["n2"], y, Mc, Cd, 1e-6)
-                gemm(blk["fc1"], y, Mc, hid, ACT_GELU)
-                gemm(blk["fc2"], hid, Mc, x, res=x)
+            vit_encoder_blocks(self.engine, L, P["blocks"], x, y, qkv, att, hid, nB, T, VIT_HEADS, VIT_HDIM, 1e-6, scale, sh)
             feat = cbuf("vit_feat", Mc * Cd)
             lnorm(x, P["last"], feat, Mc, Cd, 1e-6, addvec=ptr(kpe, lo * Cd) if kpe is not None else None, rpv=T)   # last_norm, + kpe (model.py:102-104)
             # decoder head (mano_head.py:58-112)
@@ -408,22 +398,15 @@ class HAMER(EngineSwitches, nn.Module):
         if nch == 1:
             pipeline(0, B2, main, "c0")
         else:
-            ev0 = torch.cuda.Event()
-            ev0.record(main)
-            done = []
+            chunks = SideJobs(main)
             for ci in range(nch):
                 lo, hi = ci * B2 // nch, (ci + 1) * B2 // nch
                 st = main if ci == nch - 1 else self._side_stream(dev, ci)
-                if st is not main:
-                    st.wait_event(ev0)
+                chunks.begin(st)
                 with torch.cuda.stream(st):
                     pipeline(lo, hi - lo, st, f"c{ci}")
-                if st is not main:
-                    ev = torch.cuda.Event()
-                    ev.record(st)
-                    done.append(ev)
-            for ev in done:
-                main.wait_event(ev)
+                chunks.end(st)
+            chunks.join()
         rot = torch.empty(B2, 16, 3, 3, device=dev)
         check(L.hands_rot6d_to_matrix_cols_f32(ptr(pred), 112, ptr(rot), B2, stream), "rot6d_cols")
         shape = pred[:, 96:106].contiguous()

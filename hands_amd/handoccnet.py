@@ -15,7 +15,7 @@ Mirror of the reference ``HandOccNet(focal_length, img_res, args)``
                                                            hands_pool2x2, hands_upsample_nearest2x_add_f32,
                                                            hands_spatial_softmax_f32
     mano_head.py:190-207 MLP regressor, rot6d (columns)    GEMMs, hands_rot6d_to_matrix_cols_f32
-    model.py:103-120  MANOHead x2, grasp MLP               shared with hands_light
+    model.py:103-120  MANOHead x2, grasp MLP               hands_amd.mano_head; the same kernels as hands_light
 """
 from __future__ import annotations
 
@@ -25,10 +25,11 @@ import torch.nn as nn
 from . import _lib
 from ._lib import ACT_GELU, ACT_LEAKY_RELU, ACT_NONE, ACT_RELU, check, ptr
 from .engine import ConvEngine, EngineSwitches
-from .hands_light import MANOHead, _Args, mano_consts, run_mano_heads
-from .packing import BN_EPS, PackedConv, fold_bn, pack_conv, pack_linear, pack_mano
+from .mano_head import MANOHead, pack_mano_pair, run_mano_heads
+from .packing import BN_EPS, PackedConv, fold_bn, hmr_decoder_rows, pack_conv, pack_linear
 from .param_tree import build_tree, load_manifest
-from .xdict import stream_xdict, xdict
+from .streams import SideJobs
+from .xdict import _Args, args_getter, stream_xdict, xdict
 
 HANDOCC_DEFAULT_ARGS = _Args(pos_enc="center+corner_latent", n_freq_pos_enc=4, use_grasp_loss=True,
                              use_render_seg_loss=False, img_res=224, focal_length=1000.0,
@@ -83,7 +84,7 @@ class HandOccNet(EngineSwitches, nn.Module):
     def __init__(self, focal_length=1000.0, img_res=224, args=None, mano_assets=None):
         super().__init__()
         args = args if args is not None else HANDOCC_DEFAULT_ARGS
-        get = args.get if hasattr(args, "get") else (lambda k, d=None: getattr(args, k, d))
+        get = args_getter(args)
         self.args = args
         # built: pos_enc 'center+corner_latent' (shipped) or None (model.py:74-89: no KPE anywhere), grasp head on or off;
         # 'dense_latent' fails in the reference's own PositionalEncoding (hamer_light/pos_emb.py:41 calls compute_dense_pos_enc
@@ -266,18 +267,14 @@ class HandOccNet(EngineSwitches, nn.Module):
         P["base2"] = lin(mp + ".mano_base_layer.2")
         wd = torch.cat([sd[mp + ".pose_reg.weight"], sd[mp + ".shape_reg.weight"], sd[mp + ".cam_reg.weight"]], 0)
         bd = torch.cat([sd[mp + ".pose_reg.bias"], sd[mp + ".shape_reg.bias"], sd[mp + ".cam_reg.bias"]], 0)
-        rows = list(range(96)) + [96 + i for i in range(10)] + [108 + i for i in range(3)]
-        P["regs"] = pack_linear(wd, bd, dev, row_index=rows, n_total=112)
+        P["regs"] = pack_linear(wd, bd, dev, row_index=hmr_decoder_rows(), n_total=112)
         P["regs"].acc64 = "mlp" in self.acc64_stages
         if self.use_grasp_loss:
             gcol = [144 + i for i in range(10)] + list(range(144))
             P["g0"] = lin("grasp_classifier.0", col_index=gcol, k_total=154)
             P["g2"], P["g4"] = lin("grasp_classifier.2"), lin("grasp_classifier.4")
             P["g6"] = lin("grasp_classifier.6", n_total=12)
-        for side, head in (("mano_r", self.mano_r), ("mano_l", self.mano_l)):
-            m = pack_mano(head.mano.asset(), dev)
-            m["consts"] = mano_consts(m)
-            P[side] = m
+        P["mano_r"], P["mano_l"] = pack_mano_pair(self.mano_r, self.mano_l, dev)
         return P
 
     def packed(self, dev):
@@ -558,24 +555,18 @@ class HandOccNet(EngineSwitches, nn.Module):
         else:
             # chunks of crops on separate streams: a launch is a few hundred workgroups on 256 CUs, and
             # the other chunk's workgroups fill its tail (same idea as HandsLight.trunk_chunks)
-            ev0 = torch.cuda.Event()
-            ev0.record(main)
-            parts, done = [], []
+            chunks, parts = SideJobs(main), []
             for ci in range(nch):
                 lo, hi = ci * B2 // nch, (ci + 1) * B2 // nch
                 st = main if ci == nch - 1 else self._side_stream(dev, ci)
-                if st is not main:
-                    st.wait_event(ev0)
+                chunks.begin(st)
                 with torch.cuda.stream(st):
                     pc_ = pipeline(x4[lo:hi], center[lo:hi].contiguous(), corner[lo:hi].contiguous(), hi - lo, st.cuda_stream)
                 if st is not main:
                     pc_.record_stream(main)
-                    ev = torch.cuda.Event()
-                    ev.record(st)
-                    done.append(ev)
+                chunks.end(st)
                 parts.append(pc_)
-            for ev in done:
-                main.wait_event(ev)
+            chunks.join()
             pred = torch.cat(parts, 0)
         rot = new(B2, 16, 3, 3)
         check(L.hands_rot6d_to_matrix_cols_f32(ptr(pred), 112, ptr(rot), B2, stream), "rot6d_cols")

@@ -36,285 +36,28 @@ grasp head with / without the global feature vector or absent, ``separate_hands`
 ``use_glb_feat=False``, ``use_depth_loss`` (the depth head); the constructor keyword tf_decoder=True with pos_enc 'center+corner_latent', 'dense_latent' or
 None (the reference itself fails on tf_decoder with 'sinusoidal_cc', 'cam_conv', ``no_crops`` or ``regress_center_corner``);
 backbone='resnet18' and the renderer switch raise ``NotImplementedError``.
+
+This file is the model: its defaults, constructor switches, packing and forward orchestration, workspaces and streams.  The
+trunks are ``resnet50.py`` / ``vit_b16.py``, the HandHMR, transformer and depth heads ``hmr_head.py``, the MANO head
+``mano_head.py``, the fork / join of side-stream jobs ``streams.py``.
 """
 from __future__ import annotations
-
-import ctypes as C
-import types
 
 import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import ManoConsts, ManoOut, ManoSide, check, ptr
+from ._lib import check, ptr
 from .engine import DEFAULT_ENGINE, ConvEngine, EngineSwitches
-from .mano import ManoLayer, build_mano_asset
-from .packing import (BN_EPS, HMR_VEC, PackedConv, fold_bn, hmr_state_columns, pack_conv, pack_conv1x1_dual,
-                      pack_linear, pack_mano)
-from .vit_b16 import (VITB_DIM, VITB_GRID, VITB_HDIM, VITB_HEADS, VITB_LN_EPS, VITB_MLP, VITB_RES, VITB_TOKENS, ViTB16Params,
-                      vit_conv_params)
-from .xdict import prefix_dict, stream_xdict, xdict
+from .hmr_head import TF_PASS, HandHMR, depth_head, pack_hmr_head, tf_head
+from .mano_head import MANOHead, ManoHeadsPlan, pack_mano_pair, run_mano_heads  # noqa: F401  (ManoHeadsPlan: importable from here)
+from .packing import HMR_VEC, pack_conv, pack_linear
+from .resnet50 import ResNet50Params, pack_resnet50_trunk, resnet50_trunk
+from .streams import SideJobs
+from .vit_b16 import ViTB16Params, pack_vit_b16_trunk, vit_b16_trunk, vit_conv_params
+from .xdict import _Args, args_getter, stream_xdict, xdict
 
-RESNET50_LAYERS = (3, 4, 6, 3)
 BACKBONES = ("resnet50", "vit_b_16")      # model.py:19-31 also names resnet18: not built
-
-
-# --------------------------------------------------------------------------------------------------
-# parameter containers (names = the reference's state_dict keys; never called)
-# --------------------------------------------------------------------------------------------------
-class _Bottleneck(nn.Module):
-    """resnet.py:99-154 parameter layout (conv1/bn1/conv2/bn2/conv3/bn3/downsample.{0,1})."""
-
-    def __init__(self, inplanes, planes, stride, downsample):
-        super().__init__()
-        self.conv1 = nn.Conv2d(inplanes, planes, 1, bias=False)
-        self.bn1 = nn.BatchNorm2d(planes)
-        self.conv2 = nn.Conv2d(planes, planes, 3, stride=stride, padding=1, bias=False)
-        self.bn2 = nn.BatchNorm2d(planes)
-        self.conv3 = nn.Conv2d(planes, planes * 4, 1, bias=False)
-        self.bn3 = nn.BatchNorm2d(planes * 4)
-        self.stride = stride
-        if downsample:
-            self.downsample = nn.Sequential(nn.Conv2d(inplanes, planes * 4, 1, stride=stride, bias=False),
-                                            nn.BatchNorm2d(planes * 4))
-        else:
-            self.downsample = None
-
-
-class ResNet50Params(nn.Module):
-    """resnet.py:157-280 parameter layout of the ResNet-50 trunk (no avgpool/fc)."""
-
-    def __init__(self, in_ch=3):
-        super().__init__()
-        self.conv1 = nn.Conv2d(in_ch, 64, 7, stride=2, padding=3, bias=False)
-        self.bn1 = nn.BatchNorm2d(64)
-        inplanes = 64
-        for li, (planes, n) in enumerate(zip((64, 128, 256, 512), RESNET50_LAYERS), start=1):
-            blocks = []
-            for bi in range(n):
-                stride = 2 if (bi == 0 and li > 1) else 1
-                blocks.append(_Bottleneck(inplanes, planes, stride, downsample=(bi == 0)))
-                inplanes = planes * 4
-            setattr(self, f"layer{li}", nn.Sequential(*blocks))
-
-
-class _HMRLayerParams(nn.Module):
-    """hmr_layer.py:7-62 (tf_decoder=False)."""
-
-    def __init__(self, feat_dim, mid_dim, specs):
-        super().__init__()
-        hmr_dim = feat_dim + sum(specs.values())
-        self.refine = nn.Sequential(nn.Linear(hmr_dim, mid_dim), nn.ReLU(), nn.Dropout(),
-                                    nn.Linear(mid_dim, mid_dim), nn.ReLU(), nn.Dropout())
-        self.decoders = nn.ModuleDict({k: nn.Linear(mid_dim, v) for k, v in specs.items()})
-
-
-class _MHAParams(nn.Module):
-    """nn.MultiheadAttention's parameter layout (packed in_proj rows [q | k | v], out_proj as a Linear)."""
-
-    def __init__(self, dim):
-        super().__init__()
-        self.in_proj_weight = nn.Parameter(torch.empty(3 * dim, dim))
-        self.in_proj_bias = nn.Parameter(torch.zeros(3 * dim))
-        self.out_proj = nn.Linear(dim, dim)
-        nn.init.xavier_uniform_(self.in_proj_weight)
-
-
-class _TFLayerParams(nn.Module):
-    """hands_light/transformer.py:398-415 (encoder layer) / :601-622 (decoder layer: + multihead_attn, norm3).  The norms are
-    never applied (the head runs both layers with no_norm=True) but stay in the state_dict, as in the reference."""
-
-    def __init__(self, dim, cross):
-        super().__init__()
-        self.self_attn = _MHAParams(dim)
-        if cross:
-            self.multihead_attn = _MHAParams(dim)
-        self.linear1 = nn.Linear(dim, dim)
-        self.linear2 = nn.Linear(dim, dim)
-        self.norm1 = nn.LayerNorm(dim)
-        self.norm2 = nn.LayerNorm(dim)
-        if cross:
-            self.norm3 = nn.LayerNorm(dim)
-
-
-class _TFStack(nn.Module):
-    """TransformerDecoder / TransformerEncoder with num_layers=1: ``layers.0``."""
-
-    def __init__(self, dim, cross):
-        super().__init__()
-        self.layers = nn.ModuleList([_TFLayerParams(dim, cross)])
-
-
-class _HMRLayerTFParams(nn.Module):
-    """hmr_layer.py:7-62 with tf_decoder=True: ``refine`` is replaced by the token embeddings, one decoder layer over the
-    feature pixels and one encoder layer; ``in_dim`` is the channel count of the map the head reads."""
-
-    def __init__(self, in_dim, mid_dim, specs):
-        super().__init__()
-        self.vector_mlp = nn.Sequential(nn.Linear(1, mid_dim), nn.ReLU())
-        self.feat_mlp = nn.Sequential(nn.Linear(in_dim, mid_dim), nn.ReLU())
-        self.refine_decoder = _TFStack(mid_dim, cross=True)
-        self.self_attn = _TFStack(mid_dim, cross=False)
-        self.decoders = nn.ModuleDict({k: nn.Linear(mid_dim, v) for k, v in specs.items()})
-
-
-TF_TOKENS = 109      # one token per scalar of the vectors, in `init_vector_dict` order: pose_6d 96, shape 10, cam_t/wp 3
-TF_DIM = 1024        # d_model of the head's layers = its single head's dimension
-TF_PASS = 256        # samples per pass of the transformer head (the (109 n, 3072) in_proj output of 256 samples is 343 MB)
-
-
-class HandHMR(nn.Module):
-    """hand_hmr.py:9-44 parameter layout.  ``tf_in``: tf_decoder=True, the head reads a (tf_in, 7, 7) map."""
-
-    def __init__(self, feat_dim, is_rhand, n_iter, tf_in=None):
-        super().__init__()
-        self.is_rhand, self.n_iter = is_rhand, n_iter
-        self.hand_specs = {"pose_6d": 96, "cam_t/wp": 3, "shape": 10}
-        if tf_in is None:
-            self.hmr_layer = _HMRLayerParams(feat_dim, 1024, self.hand_specs)
-        else:
-            self.hmr_layer = _HMRLayerTFParams(tf_in, TF_DIM, self.hand_specs)
-            self.cam_init_precursor = nn.Sequential(nn.Linear(tf_in, feat_dim), nn.ReLU())
-        self.cam_init = nn.Sequential(nn.Linear(feat_dim, 512), nn.ReLU(), nn.Linear(512, 512), nn.ReLU(),
-                                      nn.Linear(512, 3))
-
-
-class MANOHead(nn.Module):
-    """mano_head.py:12-19: holds the MANO layer as ``.mano``."""
-
-    def __init__(self, is_rhand, focal_length, img_res, asset=None):
-        super().__init__()
-        self.mano = ManoLayer(asset if asset is not None else build_mano_asset(is_rhand))
-        self.focal_length, self.img_res, self.is_rhand = focal_length, img_res, is_rhand
-
-    @property
-    def faces(self):
-        return self.mano.faces
-
-
-_MANO_OUT_SHAPES = (("vertices", (778, 3)), ("v3d.cam", (778, 3)), ("joints3d", (21, 3)), ("j3d.cam", (21, 3)),
-                    ("j2d.norm", (21, 2)), ("cam_t", (3,)))
-
-
-def _mano_out_buffers(bz, dev):
-    """The twelve output tensors of the two MANO heads as contiguous views of ONE allocation (one allocator call per
-    forward); the two vertex arrays come first in each side's 16-byte aligned block (the kernel stores them 8 bytes wide)."""
-    side_floats = (bz * 4839 + 3) // 4 * 4
-    flat = torch.empty(2 * side_floats, device=dev)
-    outs = []
-    for side in range(2):
-        o, off = {}, side * side_floats
-        for name, shp in _MANO_OUT_SHAPES:
-            n = bz
-            for d_ in shp:
-                n *= d_
-            o[name] = flat[off:off + n].view((bz,) + shp)
-            off += n
-        outs.append(o)
-    return outs
-
-
-def _mano_output_dict(outs, rot, shape, cam, cam_init, bz):
-    """Key order of mano_head.py:53-61 + the `cam_t.wp.init` / `mano.` prefixing of model.py:392-399."""
-    output = xdict()
-    for side, post in enumerate((".r", ".l")):
-        ro = side * bz
-        o = outs[side]
-        md = xdict()
-        md["cam_t.wp"] = cam[ro:ro + bz]
-        md["cam_t"] = o["cam_t"]
-        md["joints3d"] = o["joints3d"]
-        md["vertices"] = o["vertices"]
-        md["j3d.cam"] = o["j3d.cam"]
-        md["v3d.cam"] = o["v3d.cam"]
-        md["j2d.norm"] = o["j2d.norm"]
-        md["beta"] = shape[ro:ro + bz]
-        md["pose"] = rot[ro:ro + bz]
-        md = md.postfix(post)
-        md["cam_t.wp.init" + post] = cam_init[ro:ro + bz]       # model.py:392-393
-        output.merge(prefix_dict(md, "mano."))                  # model.py:395-399
-    return output
-
-
-class ManoHeadsPlan:
-    """``MANOHead.forward`` of both hands as ONE pre-bound C-ABI call (BASELINE configs[4], a serving loop over fixed
-    buffers): the descriptor array of ``hands_mano_heads_f32`` -- input pointers, the twelve output views, both assets'
-    constants -- is built once; ``launch(stream)`` is the single ctypes call per step and ``outputs`` the (fixed) result
-    dict.  The caller owns ``rot`` (2bz,16,3,3) [or (2bz,48) axis-angle with ``aa_input``], ``shape`` (2bz,10),
-    ``cam`` (2bz,3), ``K`` (bz,3,3) and rewrites them in place between steps."""
-
-    def __init__(self, L, mano_r, mano_l, rot, shape, cam, K, img_res, bz, aa_input=False, cam_init=None):
-        per = 48 if aa_input else 144
-        assert rot.is_contiguous() and shape.is_contiguous() and cam.is_contiguous() and K.is_contiguous()
-        assert rot.numel() == 2 * bz * per and shape.numel() == 2 * bz * 10 and cam.numel() == 2 * bz * 3 and K.numel() == bz * 9
-        self.L, self.bz, self.img_res, self.aa = L, bz, float(img_res), int(bool(aa_input))
-        self._keep = (mano_r, mano_l, rot, shape, cam, K)
-        self._outs = _mano_out_buffers(bz, rot.device)
-        self._sides = (ManoSide * 2)()
-        for side, mp in enumerate((mano_r, mano_l)):
-            ro, o = side * bz, self._outs[side]
-            mo = ManoOut(ptr(o["vertices"]), ptr(o["joints3d"]), ptr(o["v3d.cam"]), ptr(o["j3d.cam"]), ptr(o["j2d.norm"]),
-                         ptr(o["cam_t"]))
-            self._sides[side] = ManoSide(mp["consts"], ptr(mp["blend"].w), ptr(mp["blend"].bias), ptr(rot, ro * per),
-                                         ptr(shape, ro * 10), ptr(cam, ro * 3), mo)
-        self._K = ptr(K)
-        self.outputs = _mano_output_dict(self._outs, rot, shape, cam, cam if cam_init is None else cam_init, bz)
-
-    def launch(self, stream):
-        check(self.L.hands_mano_heads_f32(self._sides, 2, self._K, 10, self.img_res, 0.1, self.bz, self.aa, stream), "mano_heads")
-        return self.outputs
-
-
-def run_mano_heads(L, mano_r, mano_l, rot, shape, cam, cam_init, K, img_res, bz, stream, buf, engine=None):
-    """MANOHead.forward for the right (rows [0,bz)) and left (rows [bz,2bz)) hands
-    (src/nets/hand_heads/mano_head.py:21-65) + the `cam_t.wp.init` / `mano.` prefixing of
-    model.py:392-399.  rot (2bz,16,3,3), shape (2bz,10), cam / cam_init (2bz,3), K (bz,3,3).
-    One launch for both hands (hands_mano_heads_f32); ``engine.fuse_mano = False`` keeps the three-launch
-    chain per side (pose -> blend GEMM -> skin), which the tests compare it with."""
-    dev = rot.device
-    engine = engine or DEFAULT_ENGINE
-    fused = getattr(engine, "fuse_mano", True)
-    outs = _mano_out_buffers(bz, dev)
-    mouts = [ManoOut(ptr(o["vertices"]), ptr(o["joints3d"]), ptr(o["v3d.cam"]), ptr(o["j3d.cam"]),
-                     ptr(o["j2d.norm"]), ptr(o["cam_t"])) for o in outs]
-    if fused:
-        sides = (ManoSide * 2)()
-        for side, mp in enumerate((mano_r, mano_l)):
-            ro = side * bz
-            sides[side] = ManoSide(mp["consts"], ptr(mp["blend"].w), ptr(mp["blend"].bias), ptr(rot, ro * 144),
-                                   ptr(shape, ro * 10), ptr(cam, ro * 3), mouts[side])
-        check(L.hands_mano_heads_f32(sides, 2, ptr(K), 10, img_res, 0.1, bz, 0, stream), "mano_heads")
-    else:
-        blend_in = buf("blend_in", bz * 160)
-        Abuf, j16 = buf("mano_A", bz * 192), buf("mano_j16", bz * 48)
-        vposed = buf("vposed", bz * 2336)
-        for side, mp in enumerate((mano_r, mano_l)):
-            ro = side * bz
-            check(L.hands_mano_pose_f32(C.byref(mp["consts"]), ptr(rot, ro * 144), ptr(shape, ro * 10), 10,
-                                        ptr(blend_in), 160, ptr(Abuf), ptr(j16), bz, stream), "mano_pose")
-            engine.conv(L, mp["blend"], blend_in, bz, 1, 1, vposed, False, stream)
-            check(L.hands_mano_skin_f32(C.byref(mp["consts"]), ptr(vposed), 2336, ptr(Abuf), ptr(j16),
-                                        ptr(cam, ro * 3), ptr(K), img_res, 0.1, C.byref(mouts[side]), bz, stream),
-                  "mano_skin")
-    return _mano_output_dict(outs, rot, shape, cam, cam_init, bz)
-
-
-run_mano_heads.launches_per_step = 1
-
-
-def mano_consts(m):
-    return ManoConsts(ptr(m["pose_mean"]), ptr(m["J_template"]), ptr(m["J_shapedirs"]), ptr(m["lbs_weights"]),
-                      ptr(m["tip_ids"]))
-
-
-class _Args(dict):
-    """attribute *and* ``.get`` access, like the reference's EasyDict args (parser.py:39-58)."""
-
-    def __getattr__(self, k):
-        if k.startswith("__"):
-            raise AttributeError(k)
-        return self.get(k)
-
 
 LATENT_ENC = ("center+corner_latent", "sinusoidal_cc")
 IMAGE_ENC = {"center": 1, "corner": 2, "center+corner": 3}     # -> mode of hands_image_posenc_nhwc_f32
@@ -357,7 +100,7 @@ class HandsLight(EngineSwitches, nn.Module):
         self.async_tail = True        # tail of the forward on its own stream, joined at first use of the result
         self._calls = 0
         args = args if args is not None else DEFAULT_ARGS
-        get = (lambda k, d=None: args.get(k, d)) if hasattr(args, "get") else (lambda k, d=None: getattr(args, k, d))
+        get = args_getter(args)
         self.args = args
         if backbone not in BACKBONES:
             raise NotImplementedError(f"hands_amd.HandsLight: backbone={backbone!r} is not built (built: {BACKBONES})")
@@ -385,7 +128,7 @@ class HandsLight(EngineSwitches, nn.Module):
         self.regress_center_corner = bool(get("regress_center_corner", False))   # model.py:157-172, 426-433
         self.use_glb_feat = bool(get("use_glb_feat", False))
         # tf_decoder (model.py:34-38, 312-314): feature_conv is skipped and both heads read the concatenated 7x7 map through the
-        # transformer head (hmr_layer.py:17-42, 67-86) -- :meth:`_tf_head`
+        # transformer head (hmr_layer.py:17-42, 67-86) -- ``hmr_head.tf_head``
         # The switch is the constructor's keyword ``tf_decoder=True``, like ``backbone``.  ``args.tf_decoder`` alone keeps raising
         # NotImplementedError, as it always has here: a caller who hands over the reference's args gets the head only by asking
         # for it by name.
@@ -501,138 +244,14 @@ class HandsLight(EngineSwitches, nn.Module):
         return super()._apply(fn, *a, **k)
 
     @torch.no_grad()
-    def _pack_trunk(self, net: ResNet50Params, dev):
-        cpu = lambda t: t.detach().cpu()
-        bnp = lambda bn: (cpu(bn.weight), cpu(bn.bias), cpu(bn.running_mean), cpu(bn.running_var))
-        P = {}
-        w, b = fold_bn(cpu(net.conv1.weight), *bnp(net.bn1))
-        if w.shape[1] == 3:
-            P["stem"] = pack_conv(w, b, 2, 3, dev, cin_pad_to=4)
-            # planar form for hands_stem_conv_maxpool_nchw_f32: k = plane * 52 + tap (49 taps + 3 zero columns per plane)
-            col = [c * 52 + t for c in range(3) for t in range(49)]
-            P["stem_planar"] = pack_linear(w.reshape(64, 147), b, dev, col_index=col, k_total=160)
-            P["stem_planar"].macs_per_pixel = 64 * 147
-        else:
-            # widened conv1 (image-level encodings): the general implicit-GEMM route on an NHWC input whose channel count is
-            # padded to a multiple of 16 (hands_image_posenc_nhwc_f32 writes the zeros)
-            P["stem_wide"] = pack_conv(w, b, 2, 3, dev, cin_pad_to=(w.shape[1] + 15) // 16 * 16)
-        blocks = []
-        for li in range(1, 5):
-            for blk in getattr(net, f"layer{li}"):
-                e = {}
-                w, b = fold_bn(cpu(blk.conv1.weight), *bnp(blk.bn1)); e["c1"] = pack_conv(w, b, 1, 0, dev)
-                w, b = fold_bn(cpu(blk.conv2.weight), *bnp(blk.bn2))
-                e["c2"] = pack_conv(w, b, blk.stride, 1, dev, winograd4=li in self.winograd4_stages)
-                w, b = fold_bn(cpu(blk.conv3.weight), *bnp(blk.bn3)); e["c3"] = pack_conv(w, b, 1, 0, dev)
-                if blk.downsample is not None:
-                    w, b = fold_bn(cpu(blk.downsample[0].weight), *bnp(blk.downsample[1]))
-                    e["ds"] = pack_conv(w, b, blk.stride, 0, dev)
-                    # conv3 + downsample as ONE GEMM over K = planes + inplanes (hands_conv1x1_dual_nhwc_f32)
-                    w3, b3 = fold_bn(cpu(blk.conv3.weight), *bnp(blk.bn3))
-                    e["c3ds"] = pack_conv1x1_dual(w3, b3, w, b, dev)
-                    e["c3ds_split"] = (w3.shape[1], w.shape[1], blk.stride)
-                blocks.append(e)
-        P["blocks"] = blocks
-        return P
-
-    @torch.no_grad()
-    def _pack_vit_trunk(self, net: ViTB16Params, tail: nn.Sequential, dev):
-        """ViT-B/16 + vit_conv in kernel layout (once per load_state_dict, like the ResNet trunk): the patch embedding as a
-        16x16 / stride 16 convolution on NHWC4 (or on the padded NHWC map of the widened form), the four linears of every block
-        through pack_linear, and vit_conv's Conv2d bias + eval BatchNorm2d folded in fp64 into one 3x3 / pad 1 layer."""
-        cpu = lambda t: t.detach().cpu()
-        lin = lambda w, b: pack_linear(cpu(w), cpu(b), dev)
-        ln = lambda m: (cpu(m.weight).float().contiguous().to(dev), cpu(m.bias).float().contiguous().to(dev))
-        P = {"vit": True}
-        w, b = cpu(net.conv_proj.weight), cpu(net.conv_proj.bias)
-        if w.shape[1] == 3:
-            P["patch"] = pack_conv(w, b, 16, 0, dev, cin_pad_to=4)
-        else:
-            # widened conv_proj (image-level encodings) on the padded NHWC map.  The general implicit GEMM takes kernels of at most
-            # 15 x 15 taps when Cin != 4, so the 16 x 16 / stride 16 layer runs as TWO launches on a strip view of the same memory:
-            # 16 image rows x 224 pixels x Cp channels are 16 rows x 14 patches x (16 Cp) channels, i.e. every strip of 16 rows is an
-            # "image" (H 16, W 14, C 16 Cp) on which the patch embedding is a KH 16 x KW 1 kernel with one output row.  Its upper
-            # and lower 8 rows are one launch each (k order (kh, kw, c) is the same in both views); the second adds the first
-            # through the residual epilogue.  No copy of the map is made.
-            Cp = (w.shape[1] + 15) // 16 * 16
-            P["stem_wide"] = types.SimpleNamespace(Cin=Cp)       # what the callers ask: the padded channel count of the map
-            P["patch_halves"] = []
-            for h0 in (0, 8):
-                pc = pack_conv(w[:, :, h0:h0 + 8, :], b if h0 == 0 else None, 1, 0, dev, cin_pad_to=Cp)
-                pc.Cin, pc.KH, pc.KW = 16 * Cp, 8, 1             # the strip view of the same packed weight
-                P["patch_halves"].append(pc)
-        P["cls"] = cpu(net.class_token).float().reshape(VITB_DIM).contiguous().to(dev)
-        P["pos"] = cpu(net.encoder.pos_embedding).float().reshape(VITB_TOKENS, VITB_DIM).contiguous().to(dev)
-        P["blocks"] = []
-        for blk in net.encoder.layers:
-            at = blk.self_attention
-            P["blocks"].append({"n1": ln(blk.ln_1), "qkv": lin(at.in_proj_weight, at.in_proj_bias),
-                                "proj": lin(at.out_proj.weight, at.out_proj.bias), "n2": ln(blk.ln_2),
-                                "fc1": lin(blk.mlp[0].weight, blk.mlp[0].bias), "fc2": lin(blk.mlp[3].weight, blk.mlp[3].bias)})
-        P["last"] = ln(net.encoder.ln)
-        # vit_conv (utils.py:27-34): y = relu(bn(conv(x) + cb)) = relu(conv'(x) + b'), w' = w g / sqrt(var + eps),
-        # b' = (cb - mean) g / sqrt(var + eps) + beta, all in fp64 and rounded to fp32 once by pack_conv.  Winograd F(2x2,3x3)
-        # weights only: at 1.4 of the trunk's 36 GFLOP the F(4x4) form has nothing to win and its larger rounding error to lose.
-        conv, bn = tail[1], tail[2]
-        sc = cpu(bn.weight).double() / torch.sqrt(cpu(bn.running_var).double() + BN_EPS)
-        wf = cpu(conv.weight).double() * sc[:, None, None, None]
-        bf = (cpu(conv.bias).double() - cpu(bn.running_mean).double()) * sc + cpu(bn.bias).double()
-        P["vit_conv"] = pack_conv(wf, bf, 1, 1, dev)
-        return P
-
-    @torch.no_grad()
-    def _pack_head(self, head: HandHMR, dev):
-        cpu = lambda t: t.detach().cpu()
-        F = self.feat_dim
-        P = {}
-        ci = head.cam_init
-        P["ci0"] = pack_linear(cpu(ci[0].weight), cpu(ci[0].bias), dev)
-        P["ci2"] = pack_linear(cpu(ci[2].weight), cpu(ci[2].bias), dev)
-        P["ci4"] = pack_linear(cpu(ci[4].weight), cpu(ci[4].bias), dev, n_total=4)
-        hl = head.hmr_layer
-        if self.tf_decoder:
-            # every Linear of the transformer head as a pointwise GEMM; the cross-attention in_proj is cut into its query rows
-            # (applied to the tokens, every iteration) and its key | value rows (applied to `memory`, once per forward)
-            lin = lambda m: pack_linear(cpu(m.weight), cpu(m.bias), dev)
-            E = TF_DIM
-            dl, el = hl.refine_decoder.layers[0], hl.self_attn.layers[0]
-            xw, xb = cpu(dl.multihead_attn.in_proj_weight), cpu(dl.multihead_attn.in_proj_bias)
-            P["tf"] = {
-                "pre": lin(head.cam_init_precursor[0]), "feat_mlp": lin(hl.feat_mlp[0]),
-                "vec_w": cpu(hl.vector_mlp[0].weight).float().reshape(E).contiguous().to(dev),
-                "vec_b": cpu(hl.vector_mlp[0].bias).float().contiguous().to(dev),
-                "d_qkv": pack_linear(cpu(dl.self_attn.in_proj_weight), cpu(dl.self_attn.in_proj_bias), dev),
-                "d_proj": lin(dl.self_attn.out_proj),
-                "x_q": pack_linear(xw[:E], xb[:E], dev), "x_kv": pack_linear(xw[E:], xb[E:], dev),
-                "x_proj": lin(dl.multihead_attn.out_proj), "d_l1": lin(dl.linear1), "d_l2": lin(dl.linear2),
-                "e_qkv": pack_linear(cpu(el.self_attn.in_proj_weight), cpu(el.self_attn.in_proj_bias), dev),
-                "e_proj": lin(el.self_attn.out_proj), "e_l1": lin(el.linear1), "e_l2": lin(el.linear2)}
-            # cam_t.wp.init = 1 + an O(0.1) read-out: its error is the final rounding plus what the four layers in front of it
-            # pass on.  The reference's fp32 value is within 0.3-0.8 ulp of its fp64 run, so the layers are accumulated in fp64
-            # (HANDS_ACC_F64: correctly rounded fp32 outputs; the precursor is 4 % of the head's work at half the matrix rate)
-            for pc in (P["tf"]["pre"], P["ci0"], P["ci2"], P["ci4"]):
-                pc.acc64 = True
-        else:
-            rf = hl.refine
-            P["r0"] = pack_linear(cpu(rf[0].weight), cpu(rf[0].bias), dev, col_index=hmr_state_columns(F),
-                                  k_total=F + HMR_VEC)
-            P["r3"] = pack_linear(cpu(rf[3].weight), cpu(rf[3].bias), dev)
-        d = hl.decoders
-        wd = torch.cat([cpu(d["pose_6d"].weight), cpu(d["shape"].weight), cpu(d["cam_t/wp"].weight)], 0)
-        bd = torch.cat([cpu(d["pose_6d"].bias), cpu(d["shape"].bias), cpu(d["cam_t/wp"].bias)], 0)
-        rows = list(range(96)) + [96 + i for i in range(10)] + [108 + i for i in range(3)]
-        P["dec"] = pack_linear(wd, bd, dev, row_index=rows, n_total=HMR_VEC)
-        return P
-
-    @torch.no_grad()
     def _pack(self, dev):
         cpu = lambda t: t.detach().cpu()
         F = self.feat_dim
-        P = {"head_r": self._pack_head(self.head_r, dev), "head_l": self._pack_head(self.head_l, dev)}
+        P = {"head_r": pack_hmr_head(self.head_r, dev, F, self.tf_decoder), "head_l": pack_hmr_head(self.head_l, dev, F, self.tf_decoder)}
         if self.backbone_name == "vit_b_16":
-            pack_trunk = lambda name: self._pack_vit_trunk(getattr(self, name), getattr(self, "vit_conv" if name == "backbone" else name + "_vit_conv"), dev)
+            pack_trunk = lambda name: pack_vit_b16_trunk(getattr(self, name), getattr(self, "vit_conv" if name == "backbone" else name + "_vit_conv"), dev)
         else:
-            pack_trunk = lambda name: self._pack_trunk(getattr(self, name), dev)
+            pack_trunk = lambda name: pack_resnet50_trunk(getattr(self, name), dev, self.winograd4_stages)
         if self.use_glb_feat:
             P["backbone"] = pack_trunk("backbone")
         if not self.no_crops:
@@ -672,11 +291,7 @@ class HandsLight(EngineSwitches, nn.Module):
             P["g2"] = pack_linear(cpu(g[2].weight), cpu(g[2].bias), dev)
             P["g4"] = pack_linear(cpu(g[4].weight), cpu(g[4].bias), dev)
             P["g6"] = pack_linear(cpu(g[6].weight), cpu(g[6].bias), dev, n_total=12)
-        P["mano_r"] = pack_mano(self.mano_r.mano.asset(), dev)
-        P["mano_l"] = pack_mano(self.mano_l.mano.asset(), dev)
-        for side in ("mano_r", "mano_l"):
-            m = P[side]
-            m["consts"] = mano_consts(m)
+        P["mano_r"], P["mano_l"] = pack_mano_pair(self.mano_r, self.mano_l, dev)
         return P
 
     def _cat_ld(self):
@@ -731,124 +346,12 @@ class HandsLight(EngineSwitches, nn.Module):
     _conv = staticmethod(lambda *a, **kw: DEFAULT_ENGINE.conv(*a, **kw))
     _conv_dual = staticmethod(lambda *a, **kw: DEFAULT_ENGINE.conv_dual(*a, **kw))
 
-    def _blocks(self, L, blocks, cur, nxt, t1, t2, ds, B, H, W, stream, final_dst, final_off):
-        """A run of bottlenecks (resnet.py:134-154) on ping-pong buffers; the last one writes ``final_dst``
-        at float offset ``final_off``.  Returns (H, W) of the output map."""
-        n = len(blocks)
-        for i, e in enumerate(blocks):
-            self.engine.conv(L, e["c1"], cur, B, H, W, t1, True, stream)
-            last = i + 1 == n
-            dst, off = (final_dst, final_off) if last else (nxt, 0)
-            H2, W2 = self.engine.conv(L, e["c2"], t1, B, H, W, t2, True, stream)
-            if "ds" in e and self.engine.fuse_downsample:
-                self.engine.conv_dual(L, e["c3ds"], e["c3ds_split"], t2, cur, B, H2, W2, H, W, dst, stream, out_off=off)
-            else:
-                if "ds" in e:
-                    self.engine.conv(L, e["ds"], cur, B, H, W, ds, False, stream)
-                    ident = ds
-                else:
-                    ident = cur
-                self.engine.conv(L, e["c3"], t2, B, H2, W2, dst, True, stream, res=ident, out_off=off)
-            H, W = H2, W2
-            cur, nxt = dst, cur
-        return H, W
-
     def _trunk(self, L, P, segs, B, res_in, stream, tag, cap_B, out=None, out_off=0):
-        """ResNet-50 trunk on B images given as NCHW segments ``[(tensor, first image, n images), ...]`` (the
-        reference's input layout, read in place); returns (B,7,7,2048) features (flat tensor).
-        (Running stem + layer1 + layer2 per sub-batch of 32-128 images, to keep their HBM-bound 1x1 layers'
-        tensors inside the 256 MB Infinity Cache, was measured 1-18 % SLOWER than whole-job launches.)
-        A ViT-B/16 parameter set takes :meth:`_trunk_vit`: same contract."""
-        if "vit" in P:
-            return self._trunk_vit(L, P, segs, B, res_in, stream, tag, cap_B, out, out_off)
+        """One trunk job on this model's engine and workspaces: ``resnet50_trunk``, or ``vit_b16_trunk`` for a ViT-B/16
+        parameter set (same contract): B images as NCHW segments -> (B,7,7,2048) features."""
         dev = segs[0][0].device
-        per = 112 * 112 * 64 * (res_in * res_in) // (224 * 224) + 64      # floats per image of the largest map
-        cap = cap_B * per
-        a = self._buf("trunk_a_" + tag, cap, dev); b = self._buf("trunk_b_" + tag, cap, dev)
-        t1 = self._buf("trunk_t1_" + tag, cap, dev); t2 = self._buf("trunk_t2_" + tag, cap, dev)
-        ds = self._buf("trunk_ds_" + tag, cap, dev)
-        Hs, Ws = (res_in - 1) // 2 + 1, (res_in - 1) // 2 + 1                # stem conv map
-        Hp, Wp = (Hs + 2 - 3) // 2 + 1, (Ws + 2 - 3) // 2 + 1                # after the max-pool
-        img_floats = 3 * res_in * res_in
-        done = 0
-        for src, first, n in segs:
-            if "stem_wide" in P:
-                # widened conv1 (image-level encodings): `src` is the NHWC (.., res, res, Cpad) tensor hands_image_posenc_nhwc_f32
-                # wrote; general implicit GEMM + the max-pool kernel
-                Cp = P["stem_wide"].Cin
-                self.engine.conv(L, P["stem_wide"], src, n, res_in, res_in, a, True, stream, x_off=first * res_in * res_in * Cp)
-                check(L.hands_maxpool3x3s2_nhwc_f32(ptr(a), ptr(b, done * Hp * Wp * 64), n, Hs, Ws, 64, stream), "maxpool")
-            elif self.engine.fuse_stem_pool:
-                # conv1 + bn1 + relu + maxpool in one kernel straight from the NCHW image: neither the NHWC copy
-                # of the input nor the 112x112x64 map ever reaches HBM
-                self.engine.stem_pool_nchw(L, P["stem_planar"], src, first * img_floats, b, done * Hp * Wp * 64, n,
-                                           res_in, res_in, 1, stream)
-            else:
-                x4 = self._buf("trunk_x4_" + tag, cap_B * res_in * res_in * 4, dev)
-                check(L.hands_nchw3_to_nhwc4_f32(ptr(src, first * img_floats), ptr(x4), n, res_in, res_in, stream), "nchw->nhwc4")
-                self.engine.conv(L, P["stem"], x4, n, res_in, res_in, a, True, stream)
-                check(L.hands_maxpool3x3s2_nhwc_f32(ptr(a), ptr(b, done * Hp * Wp * 64), n, Hs, Ws, 64, stream), "maxpool")
-            done += n
-        assert done == B
-        feat = out if out is not None else self._buf("feat_" + tag, B * 49 * P["blocks"][-1]["c3"].Cout, dev)
-        H, W = self._blocks(L, P["blocks"], b, a, t1, t2, ds, B, Hp, Wp, stream, feat, out_off)
-        return feat, H, W
-
-    def _trunk_vit(self, L, P, segs, B, res_in, stream, tag, cap_B, out=None, out_off=0):
-        """``vit_forward`` (model.py:483-493) on B images given as the segments of :meth:`_trunk`; writes (B,7,7,2048) NHWC
-        features at float offset ``out_off``.  conv_proj as a 16x16 / stride 16 GEMM -> class token + position embedding
-        (hands_vit_tokens_f32) -> 12 x [LayerNorm, qkv GEMM, hands_attention_f32 (197 tokens, 12 heads x 64), out_proj GEMM +
-        residual, LayerNorm, fc1 GEMM + exact GELU, fc2 GEMM + residual] -> encoder.ln on the patch tokens + 2x2 average
-        (hands_vit_tail_f32) -> vit_conv (3x3, BatchNorm folded, ReLU).  Token-major rows are NHWC already: the reference's
-        permute + reshape to (B,768,14,14) never happens.  Workspaces are sized for M = cap_B * 197 rows and kept."""
-        if res_in != VITB_RES:
-            raise ValueError(f"hands_amd.HandsLight: the ViT-B/16 backbone takes {VITB_RES}x{VITB_RES} images, not {res_in}")
-        dev = segs[0][0].device
-        T, Cd, G = VITB_TOKENS, VITB_DIM, VITB_GRID
-        M, capM = B * T, cap_B * T
-        x = self._buf("vit_x_" + tag, capM * Cd, dev); y = self._buf("vit_y_" + tag, capM * Cd, dev)
-        att = self._buf("vit_att_" + tag, capM * Cd, dev)
-        qkv = self._buf("vit_qkv_" + tag, capM * 3 * Cd, dev); hid = self._buf("vit_h_" + tag, capM * VITB_MLP, dev)
-        gemm = lambda pc, src, dst, act=0, **kw: self.engine.conv(L, pc, src, M, 1, 1, dst, act, stream, **kw)
-        lnorm = lambda src, gb, dst: check(L.hands_layernorm_f32(ptr(src), ptr(gb[0]), ptr(gb[1]), ptr(dst), None, 1, M, Cd, VITB_LN_EPS,
-                                                                 stream), "layernorm")
-        # -- conv_proj (`_process_input`): patch rows (B,196,768) into `y`, which the first LayerNorm overwrites afterwards
-        done = 0
-        for src, first, n in segs:
-            if "stem_wide" in P:       # NHWC (.., 224, 224, Cpad) map of the image-level encodings: two launches on its strip view
-                Cp = P["stem_wide"].Cin
-                top, bottom = P["patch_halves"]
-                img = res_in * res_in * Cp
-                step = max(1, (1 << 31) // img - 1)            # the library indexes one launch's input with 31 bits
-                for c0 in range(0, n, step):
-                    nc = min(step, n - c0)
-                    xo, oo = (first + c0) * img, (done + c0) * G * G * Cd
-                    self.engine.conv(L, top, src, nc * G, 16, G, y, False, stream, x_off=xo, out_off=oo, out_hw=(1, G))
-                    self.engine.conv(L, bottom, src, nc * G, 16, G, y, False, stream, x_off=xo + 8 * res_in * Cp, out_off=oo,
-                                     res=y, res_off=oo, out_hw=(1, G))
-                hw = (G, G)
-            else:
-                x4 = self._buf("vit_x4_" + tag, cap_B * res_in * res_in * 4, dev)
-                check(L.hands_nchw3_to_nhwc4_f32(ptr(src, first * 3 * res_in * res_in), ptr(x4), n, res_in, res_in, stream), "nchw->nhwc4")
-                hw = self.engine.conv(L, P["patch"], x4, n, res_in, res_in, y, False, stream, out_off=done * G * G * Cd)
-            assert hw == (G, G)
-            done += n
-        assert done == B
-        check(L.hands_vit_tokens_f32(ptr(y), ptr(P["cls"]), ptr(P["pos"]), ptr(x), B, T, Cd, stream), "vit_tokens")
-        scale = float(VITB_HDIM) ** -0.5
-        for blk in P["blocks"]:
-            lnorm(x, blk["n1"], y)
-            gemm(blk["qkv"], y, qkv)
-            check(L.hands_attention_f32(ptr(qkv), ptr(att), B, T, VITB_HEADS, VITB_HDIM, scale, stream), "attention")
-            gemm(blk["proj"], att, x, res=x)
-            lnorm(x, blk["n2"], y)
-            gemm(blk["fc1"], y, hid, _lib.ACT_GELU)
-            gemm(blk["fc2"], hid, x, res=x)
-        # -- encoder.ln on tokens 1..196 + AvgPool2d(2) -> (B,7,7,768) in `att`; vit_conv -> the caller's feature rows
-        check(L.hands_vit_tail_f32(ptr(x), ptr(P["last"][0]), ptr(P["last"][1]), ptr(att), B, G, Cd, VITB_LN_EPS, stream), "vit_tail")
-        feat = out if out is not None else self._buf("feat_" + tag, B * 49 * P["vit_conv"].Cout, dev)
-        H, W = self.engine.conv(L, P["vit_conv"], att, B, G // 2, G // 2, feat, True, stream, out_off=out_off)
-        return feat, H, W
+        trunk = vit_b16_trunk if "vit" in P else resnet50_trunk
+        return trunk(self.engine, lambda name, numel: self._buf(name, numel, dev), L, P, segs, B, res_in, stream, tag, cap_B, out, out_off)
 
     # ---- forward ------------------------------------------------------------------------------
     @torch.no_grad()
@@ -953,22 +456,15 @@ class HandsLight(EngineSwitches, nn.Module):
                 if hi > bz:
                     segs.append((l_img, max(lo, bz) - bz, hi - max(lo, bz)))
             jobs.append((P[("hand_backbone_r", "hand_backbone_l")[c]] if self.separate_hands else P["hand_backbone"], segs, lo, hi - lo, feath))
-        ev0 = torch.cuda.Event()
-        ev0.record(main)
+        side_jobs = SideJobs(main)
         fh = fw = 7
-        done = []
         for ji, (Pt, segs, lo, n, ob) in enumerate(jobs):
             # the largest job (last) stays on the caller's stream
             st = main if (ji == len(jobs) - 1 or not self.engine.overlap) else self._side_stream(dev, f"side{ji}")
-            if st is not main:
-                st.wait_event(ev0)
+            side_jobs.begin(st)
             _, fh, fw = self._trunk(L, Pt, segs, n, res, st.cuda_stream, f"j{ji}", n, out=ob, out_off=lo * 49 * F)
-            if st is not main:
-                ev = torch.cuda.Event()
-                ev.record(st)
-                done.append(ev)
-        for ev in done:          # join only after every job has been enqueued
-            main.wait_event(ev)
+            side_jobs.end(st)
+        side_jobs.join()         # only after every job has been enqueued
         assert fh * fw == 49
         HW = fh * fw
         # small per-sample inputs the tail reads: private copies made on the caller's stream (center / corner above)
@@ -993,103 +489,6 @@ class HandsLight(EngineSwitches, nn.Module):
         self._ws[f"tail_done{par}"] = ready
         return stream_xdict(output, ready, dev)
 
-    def _depth_head(self, L, P, dev, stream, cat, B2, bz, fh, fw):
-        """`predict_depth` (model.py:177-185, 438-441) on the map feature_conv reads: (x, y) grid channels appended, eight 3x3 / pad 1
-        convolutions, three align_corners upsamplings (7 -> 28 -> 112 -> 224).  Returns (depth.r, depth.l), each (bz, 224, 224)."""
-        F = self.feat_dim
-        Cr, lda, ldd = F + self.latent_channels, (self._cat_ld() if self.enc_mode in ("latent", "dense_latent") else F), self._depth_ld()
-        d = P["depth"]
-        out = torch.empty(B2, 16 * fh * 2, 16 * fw * 2, device=dev)
-        step = 256                       # images per pass: the 224 x 224 x 32 map of 256 crops is 1.6 GB (and < 2^31 floats)
-        for lo in range(0, B2, step):
-            n = min(step, B2 - lo)
-            buf = lambda nm, numel: self._buf(nm, numel, dev)
-            din = buf("depth_in", n * fh * fw * ldd)
-            check(L.hands_concat_nhwc_f32(ptr(cat, lo * fh * fw * lda), lda, Cr, None, 0, ptr(P["depth_grid"]), 0, 2, ptr(din), ldd,
-                                          n, n, fh * fw, stream), "depth_in")
-            h, w = fh, fw
-            x = din
-            for i, pc in enumerate(d):
-                y = buf(f"depth_c{i}", n * h * w * pc.Cout)
-                self.engine.conv(L, pc, x, n, h, w, y, i < 7, stream)
-                x = y
-                if i in (1, 3, 5):                            # nn.Upsample(x4, x4, x2; bilinear, align_corners=True)
-                    k = 2 if i == 5 else 4
-                    u = buf(f"depth_u{i}", n * h * k * w * k * pc.Cout)
-                    check(L.hands_upsample_bilinear_ac_f32(ptr(x), ptr(u), n, h, w, h * k, w * k, pc.Cout, stream), "upsample_ac")
-                    x, h, w = u, h * k, w * k
-            out[lo:lo + n] = x[: n * h * w * 4].view(n, h, w, 4)[..., 0]      # Cout = 1 stored with a pixel stride of 4 floats
-        return out[:bz], out[bz:]
-
-    def _tf_head(self, L, hp, dev, stream, side, bz, HW, cat, state, caminit4):
-        """``HandHMR.forward(features, use_pool=False)`` with tf_decoder=True (hand_hmr.py:57-62, 73-92; hmr_layer.py:67-86) for one
-        hand: rows [side bz, (side + 1) bz) of the concatenated map ``cat`` (B2, HW, Cc) -> the vector columns of its ``state``
-        rows (ld 112) and its ``caminit4`` rows.
-
-          cam_init_precursor per pixel (GEMM + ReLU) -> average pool -> cam_init MLP -> hands_hmr_init_f32
-          memory = feat_mlp(pixels) and the cross-attention k | v = in_proj[E:](memory): ONCE, they do not change between iterations
-          3 x [ hands_vector_tokens_f32 (109 tokens) -> decoder layer: self-attention, cross-attention, FFN -> encoder layer:
-                self-attention, FFN -> hands_token_mean_f32 -> decoders GEMM + residual on the vectors ]
-
-        Every residual is the GEMM's epilogue (x = x + f(x), no norm: no_norm=True); attention is hands_wide_attention_f32 reading
-        the packed in_proj output in place.  Samples are walked in passes of ``tf_pass`` (256) so that the workspaces stop growing at
-        bz = 256; every kernel's rows are per sample, so a sample's result does not depend on the pass it falls in."""
-        T, E, F, Cc = TF_TOKENS, TF_DIM, self.feat_dim, self._cat_ld() if self.enc_mode in ("latent", "dense_latent") else self.feat_dim
-        tf = hp["tf"]
-        assert tf["feat_mlp"].Cin == Cc and tf["pre"].Cin == Cc
-        cap = min(bz, self.tf_pass)
-        buf = lambda nm, numel: self._buf(f"tf_{nm}{side}", numel, dev)
-        mem, kv, pre, pooled = buf("mem", cap * HW * E), buf("kv", cap * HW * 2 * E), buf("pre", cap * HW * F), buf("pool", cap * F)
-        h512a, h512b = buf("h512a", cap * 512), buf("h512b", cap * 512)
-        x, att, q, hid = buf("x", cap * T * E), buf("att", cap * T * E), buf("q", cap * T * E), buf("hid", cap * T * E)
-        qkv, xc = buf("qkv", cap * T * 3 * E), buf("xc", cap * E)
-        scale = float(E) ** -0.5
-        conv = self.engine.conv
-
-        def attention(qb, kb, koff, ldk, Tk, n):
-            """softmax(scale q k^T) v: q rows of ``qb`` (ld of its own width), k | v side by side in ``kb`` from column ``koff``"""
-            ldq = 3 * E if qb is kb else E
-            check(L.hands_wide_attention_f32(ptr(qb), T * ldq, ldq, ptr(kb, koff), Tk * ldk, ldk, ptr(kb, koff + E), Tk * ldk, ldk,
-                                             ptr(att), T * E, E, n, T, Tk, E, scale, stream), "wide_attention")
-
-        for lo in range(0, bz, self.tf_pass):
-            n = min(self.tf_pass, bz - lo)
-            r0 = side * bz + lo                       # first row of the pass in the (B2, ..) buffers
-            so, co, M = r0 * HMR_VEC, r0 * 4, n * T
-            # -- init_vector_dict (hand_hmr.py:46-71): cam_init_precursor per pixel BEFORE the average pool
-            conv(L, tf["pre"], cat, n * HW, 1, 1, pre, True, stream, x_off=r0 * HW * Cc)
-            check(L.hands_avgpool_nhwc_f32(ptr(pre), ptr(pooled), n, HW, F, F, stream), "avgpool")
-            conv(L, hp["ci0"], pooled, n, 1, 1, h512a, True, stream, splitk=True)
-            conv(L, hp["ci2"], h512a, n, 1, 1, h512b, True, stream, splitk=True)
-            conv(L, hp["ci4"], h512b, n, 1, 1, caminit4, False, stream, out_off=co)
-            check(L.hands_hmr_init_f32(ptr(state, so), ptr(caminit4, co), n, HMR_VEC, 0, stream), "hmr_init")
-            # -- memory and the cross-attention keys | values
-            conv(L, tf["feat_mlp"], cat, n * HW, 1, 1, mem, True, stream, x_off=r0 * HW * Cc)
-            conv(L, tf["x_kv"], mem, n * HW, 1, 1, kv, False, stream)
-            for _ in range(3):
-                # tokens in `init_vector_dict` order: pose_6d 96, shape 10 (state columns 0..105), cam_t/wp 3 (columns 108..110)
-                check(L.hands_vector_tokens_f32(ptr(state, so), HMR_VEC, 106, 2, ptr(tf["vec_w"]), ptr(tf["vec_b"]), ptr(x), n, T, E,
-                                                stream), "vector_tokens")
-                # decoder layer (transformer.py:652-658): self-attention, cross-attention over the pixels, FFN
-                conv(L, tf["d_qkv"], x, M, 1, 1, qkv, False, stream)
-                attention(qkv, qkv, E, 3 * E, T, n)
-                conv(L, tf["d_proj"], att, M, 1, 1, x, False, stream, res=x)
-                conv(L, tf["x_q"], x, M, 1, 1, q, False, stream)
-                attention(q, kv, 0, 2 * E, HW, n)
-                conv(L, tf["x_proj"], att, M, 1, 1, x, False, stream, res=x)
-                conv(L, tf["d_l1"], x, M, 1, 1, hid, True, stream)
-                conv(L, tf["d_l2"], hid, M, 1, 1, x, False, stream, res=x)
-                # encoder layer (transformer.py:533-539): self-attention, FFN
-                conv(L, tf["e_qkv"], x, M, 1, 1, qkv, False, stream)
-                attention(qkv, qkv, E, 3 * E, T, n)
-                conv(L, tf["e_proj"], att, M, 1, 1, x, False, stream, res=x)
-                conv(L, tf["e_l1"], x, M, 1, 1, hid, True, stream)
-                conv(L, tf["e_l2"], hid, M, 1, 1, x, False, stream, res=x)
-                # token mean, then the three decoders' residual update of the vectors (hmr_layer.py:78, 82-83)
-                check(L.hands_token_mean_f32(ptr(x), ptr(xc), n, T, E, stream), "token_mean")
-                conv(L, hp["dec"], xc, n, 1, 1, state, False, stream, res=state, out_ps=HMR_VEC, res_ps=HMR_VEC, out_off=so,
-                     res_off=so, splitk=True)
-
     def _forward_tail(self, L, P, dev, main, bz, fh, fw, featg, feath, center, corner, K, flipped, dense_enc=None, rot_in=None):
         """Everything after the trunks (model.py:196-411), enqueued on ``main`` (the tail stream)."""
         B2, F, HW = 2 * bz, self.feat_dim, fh * fw
@@ -1102,6 +501,7 @@ class HandsLight(EngineSwitches, nn.Module):
         # HMR state rows [feat F | vectors 112] (hands_hmr_init_f32); the transformer head keeps the vectors only (`vo` = their column)
         ld, vo = (HMR_VEC, 0) if self.tf_decoder else (F + HMR_VEC, F)
         state = buf("state", B2 * ld)
+        cat_ld = self._cat_ld() if self.enc_mode in ("latent", "dense_latent") else F      # row length of `cat` below
         if self.no_crops:
             # model.py:316-318 -> HandHMR.forward(features, use_pool=True) (hand_hmr.py:73-78): both heads read the average-pooled
             # GLOBAL feature map -- written straight into the feat segment of the right and the left state rows
@@ -1122,7 +522,8 @@ class HandsLight(EngineSwitches, nn.Module):
                                               HW * Ce, Ce, ptr(cat), Cc, B2, bz, HW, stream), "concat")
             else:
                 cat = feath            # pos_enc None / image-level: feature_conv reads the crop features as they are
-            depth = self._depth_head(L, P, dev, stream, cat, B2, bz, fh, fw) if self.use_depth_loss else None
+            depth = (depth_head(self.engine, buf, L, P, dev, stream, cat, B2, bz, fh, fw, F + self.latent_channels, cat_ld, self._depth_ld())
+                     if self.use_depth_loss else None)
             # -- feature_conv (model.py:91-101, 313-314) -> HMR state rows ---------------------------
             if not self.tf_decoder:
                 f1 = buf("fc1", B2 * HW * 1024)
@@ -1137,16 +538,13 @@ class HandsLight(EngineSwitches, nn.Module):
         # -- HandHMR x2 (hand_hmr.py:73-92, hmr_layer.py:67-86) ----------------------------------
         caminit4 = buf("caminit4", B2 * 4)
         # the two heads are independent chains of latency-bound M = bz GEMMs: run them side by side
-        evh = torch.cuda.Event()
-        evh.record(main)
-        joins = []
+        heads = SideJobs(main)
         for side, hp in ((0, P["head_r"]), (1, P["head_l"])):
             hs = main if (side == 1 or not self.engine.overlap) else self._side_stream(dev, "side_head")
-            if hs is not main:
-                hs.wait_event(evh)
+            heads.begin(hs)
             sh = hs.cuda_stream
             if self.tf_decoder:
-                self._tf_head(L, hp, dev, sh, side, bz, HW, cat, state, caminit4)
+                tf_head(self.engine, buf, L, hp, sh, side, bz, HW, cat, state, caminit4, F, cat_ld, self.tf_pass)
             else:
                 h512a, h512b = buf(f"h512a{side}", bz * 512), buf(f"h512b{side}", bz * 512)
                 x1, x2 = buf(f"x1024a{side}", bz * 1024), buf(f"x1024b{side}", bz * 1024)
@@ -1161,12 +559,8 @@ class HandsLight(EngineSwitches, nn.Module):
                     self.engine.conv(L, hp["r3"], x1, bz, 1, 1, x2, True, sh, splitk=True)
                     self.engine.conv(L, hp["dec"], x2, bz, 1, 1, state, False, sh, res=state, out_ps=ld,
                                res_ps=ld, out_off=so + F, res_off=so + F, splitk=True)
-            if hs is not main:
-                ev = torch.cuda.Event()
-                ev.record(hs)
-                joins.append(ev)
-        for ev in joins:
-            main.wait_event(ev)
+            heads.end(hs)
+        heads.join()
         rotmat = buf("rotmat", B2 * 144)
         check(L.hands_rot6d_to_matrix_f32(ptr(state, vo), ld, ptr(rotmat), B2, stream), "rot6d")
         if self.rot_fix == 1:      # 'pcl' (model.py:330-334): in place on the heads' output -- the flip swap and the grasp head see it

@@ -146,6 +146,11 @@ def hmr_state_columns(F):
 HMR_VEC = 112  # width of the vector part of the state row
 
 
+def hmr_decoder_rows():
+    """packed row (of HMR_VEC) of each row of the decoders stacked as cat([pose_6d 96, shape 10, cam 3])."""
+    return list(range(96)) + [96 + i for i in range(10)] + [108 + i for i in range(3)]
+
+
 def pack_mano(asset: ManoAsset, device):
     """MANO constants for the pose / blend-GEMM / skin kernels.  hands_pack_mano_f32."""
     vt, sd, pd, Jr, hm = (_f32(a) for a in (asset.v_template, asset.shapedirs, asset.posedirs, asset.J_regressor,

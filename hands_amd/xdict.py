@@ -10,7 +10,8 @@ common/ld_utils.py:12-14) that callers of the hot path rely on:
   (xdict.py:233-241 -> common/thing.py:57-66);
 * ``has_invalid`` only *reports* NaN/Inf (xdict.py:243-258).
 
-Written from the behaviour, not from the text, of the reference.
+Written from the behaviour, not from the text, of the reference.  Also here: ``_Args`` / ``args_getter``, the shims for the
+reference's EasyDict ``args`` that the three model constructors read.
 """
 from __future__ import annotations
 
@@ -228,6 +229,20 @@ def _xd_overwrite(self, k, v):
 stream_xdict.__setitem__ = _xd_setitem
 stream_xdict.overwrite = _xd_overwrite
 stream_xdict.__hash__ = None
+
+
+class _Args(dict):
+    """attribute *and* ``.get`` access, like the reference's EasyDict args (parser.py:39-58)."""
+
+    def __getattr__(self, k):
+        if k.startswith("__"):
+            raise AttributeError(k)
+        return self.get(k)
+
+
+def args_getter(args):
+    """``get(key, default=None)`` of the ``args`` a model constructor was given: a mapping (EasyDict, ``_Args``) or a namespace."""
+    return args.get if hasattr(args, "get") else (lambda k, d=None: getattr(args, k, d))
 
 
 def prefix_dict(mydict, prefix):

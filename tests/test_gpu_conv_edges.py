@@ -83,10 +83,10 @@ FEATS = {
     "F6pixel": feat(crop="pixel"),
     "F8k16": feat(kextra=16),
     "F8k48": feat(kextra=48),
-    "F123": feat(in_gap=16, out_gap=8, res="gap"),                      # hands_light.py:1154-1163 without the alias
-    "F125": feat(in_gap=16, out_gap=8, res="alias"),                    # the HMR state update, hands_light.py:1090, 1162
-    "F24": feat(out_gap=8, res="row"),                                  # hamer.py:403
-    "F256": feat(out_gap=8, res="alias", crop="row"),                   # _trunk_vit, hands_light.py:826-828
+    "F123": feat(in_gap=16, out_gap=8, res="gap"),                      # the HMR head's cam_init / refine GEMMs (HandsLight._forward_tail) without the alias
+    "F125": feat(in_gap=16, out_gap=8, res="alias"),                    # the HMR state update (hmr_head.tf_head, HandsLight._forward_tail)
+    "F24": feat(out_gap=8, res="row"),                                  # HAMER.forward: decout + the mean parameters
+    "F256": feat(out_gap=8, res="alias", crop="row"),                   # vit_b16_trunk: the bottom patch half
     "F1268": feat(in_gap=16, out_gap=8, res="dense", crop="corner", kextra=16),
 }
 
@@ -358,7 +358,7 @@ def test_pre_entry(gk, fl, S, act, fname):
 
 
 def test_patch_halves():
-    """The 8 x 16 / stride 16 patch halves of _trunk_vit (hands_light.py:826-828) scaled down to 2 x 4 / stride 4 on 4-row strips:
+    """The 8 x 16 / stride 16 patch halves of vit_b16_trunk (the widened conv_proj) scaled down to 2 x 4 / stride 4 on 4-row strips:
     the top half writes the (1, G) row, the bottom half -- input pointer two rows further, residual = the output in place -- adds
     its half.  Together they are the 4 x 4 / stride 4 patch embedding; each launch meets its own bound."""
     L, B, G, Cin, Cout = _lib.lib(), 6, 5, 16, 140

@@ -10,6 +10,7 @@ import torch
 import hands_amd
 from hands_amd import _lib
 from hands_amd._lib import check, ptr
+from hands_amd.hmr_head import tf_head
 from hands_amd.weights import synthetic_dense_inputs, synthetic_inputs
 from oracle import hands_oracle as O
 
@@ -172,7 +173,7 @@ def tf_model():
 
 
 def test_tf_head_alone_vs_reference_fp64(golden_dir, tf_model):
-    """HandsLight._tf_head on the seeded feature map of tests/golden/tf_decoder_head.npz, both hands: the distance of every
+    """hmr_head.tf_head on the seeded feature map of tests/golden/tf_decoder_head.npz, both hands: the distance of every
     output (and of the last iteration's token mean) from the reference's fp64 run is at most 2 x the reference's own fp32 distance
     from it, per key."""
     d = np.load(os.path.join(golden_dir, "tf_decoder_head.npz"), allow_pickle=False)
@@ -188,7 +189,8 @@ def test_tf_head_alone_vs_reference_fp64(golden_dir, tf_model):
     caminit4 = torch.zeros(2 * bz, 4, device=DEV)
     rot = torch.empty(2 * bz, 16, 3, 3, device=DEV)
     for side, name in ((0, "head_r"), (1, "head_l")):
-        model._tf_head(L, P[name], dev, _stream(), side, bz, 49, cat, state, caminit4)
+        tf_head(model.engine, lambda nm, numel: model._buf(nm, numel, dev), L, P[name], _stream(), side, bz, 49, cat, state, caminit4,
+                model.feat_dim, cat.shape[-1], model.tf_pass)
     check(L.hands_rot6d_to_matrix_f32(ptr(state), 112, ptr(rot), 2 * bz, _stream()), "rot6d")
     torch.cuda.synchronize()
     worst = {}

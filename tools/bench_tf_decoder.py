@@ -3,7 +3,7 @@
 
   1. shipped mode (trunk jobs on side streams, asynchronous tail): `--warmup` forwards, then `--steps` timed forwards at `--bz`
      between two synchronisations, with the switch off and on -> ms per step and hands/s (2 hands per sample, as bench.py counts);
-  2. one-stream pass of the tf_decoder model (``overlap_trunks = False``) with the two ``_tf_head`` calls bracketed by events:
+  2. one-stream pass of the tf_decoder model (``overlap_trunks = False``) with the two ``tf_head`` calls bracketed by events:
      the head's share of the forward;
   3. hands_wide_attention_f32 alone at the head's two shapes -- 109 tokens x 109 tokens reading a packed (bz, 109, 3072) in_proj
      output, 109 tokens x 49 pixels reading a (bz, 49, 2048) k | v buffer, D = 1024, one hand's batch -- as time per call and
@@ -84,7 +84,8 @@ def main():
                 model.overlap_trunks = False
                 model(inputs, meta)
                 torch.cuda.synchronize(dev)
-                evs, real = [], model._tf_head
+                from hands_amd import hands_light as HL
+                evs, real = [], HL.tf_head
 
                 def mark():
                     ev = torch.cuda.Event(enable_timing=True)
@@ -96,12 +97,12 @@ def main():
                     real(*args, **kw)
                     mark()
 
-                model._tf_head = timed_head
+                HL.tf_head = timed_head
                 t0 = time.perf_counter()
                 model(inputs, meta)
                 torch.cuda.synchronize(dev)
                 ser_ms = (time.perf_counter() - t0) * 1e3
-                del model._tf_head
+                HL.tf_head = real
                 head_ms = sum(evs[i].elapsed_time(evs[i + 1]) for i in range(0, len(evs), 2))
                 rec["one_stream"] = {"ms_per_step": round(ser_ms, 2), "tf_head_ms_both_hands": round(head_ms, 2),
                                      "tf_head_share_of_forward": round(head_ms / ser_ms, 4)}
