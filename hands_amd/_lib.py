@@ -152,6 +152,7 @@ SIGNATURES = {
     "hands_grasp_input_f32": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P],
     "hands_mano_pose_f32": [C.POINTER(ManoConsts), _P, _P, _I, _P, _I, _P, _P, _I, _P],
     "hands_mano_heads_f32": [C.POINTER(ManoSide), _I, _P, _I, _F, _F, _I, _I, _P],
+    "hands_mano_heads_vsplit": [_I, _I],
     "hands_mano_skin_f32": [C.POINTER(ManoConsts), _P, _I, _P, _P, _P, _P, _F, _F, C.POINTER(ManoOut), _I, _P],
     "hands_resize_crop_nchw3_to_nhwc4_f32": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
     "hands_layernorm_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _P],

@@ -553,6 +553,20 @@ __global__ void __launch_bounds__(256, 2) mano_heads_kernel(ManoHeadsArgs a) {
 
 extern "C" {
 
+int hands_mano_heads_vsplit(int B, int n_sides) {
+  if (B <= 0 || n_sides < 1 || n_sides > 2) return 0;
+  // split the 13 vertex chunks over blockIdx.z until ~800 blocks (3 per CU) exist; only the splits that lower the
+  // largest per-block chunk count are candidates (results do not depend on the split).  Measured at 2048 hands:
+  // 4 -> 55 us, 7 -> 49 us, 13 -> 55 us; at 512 hands 13 is best (22 us)
+  const long long base = ((long long)B + MH - 1) / MH * n_sides;
+  const long long want = (800 + base - 1) / base;
+  int vs = NCHUNK;
+  const int cand[7] = {1, 2, 3, 4, 5, 7, 13};
+  for (int i = 6; i >= 0; --i)
+    if (cand[i] >= want) vs = cand[i];
+  return vs;
+}
+
 int hands_mano_heads_f32(const hands_mano_side* sides, int n_sides, const float* K, int ld_betas, float img_res,
                          float min_s, int B, int axis_angle_input, hands_stream_t stream) {
   if (!sides || n_sides < 1 || n_sides > 2 || !K || B <= 0 || ld_betas < 10) return HANDS_EINVAL;
@@ -563,22 +577,15 @@ int hands_mano_heads_f32(const hands_mano_side* sides, int n_sides, const float*
         !h.consts.tip_ids || !h.blend_w || !h.blend_bias || !h.rot || !h.betas || !h.cam_wp || !h.out.vertices ||
         !h.out.joints3d || !h.out.v3d_cam || !h.out.j3d_cam || !h.out.j2d_norm || !h.out.cam_t)
       return HANDS_EINVAL;
+    // the kernel stores the two vertex arrays 8 bytes wide and loads the packed blend matrix 16 bytes wide
+    if (((uintptr_t)h.out.vertices & 7u) || ((uintptr_t)h.out.v3d_cam & 7u) || ((uintptr_t)h.blend_w & 15u)) return HANDS_EINVAL;
     a.side[s].c = h.consts; a.side[s].blend_w = h.blend_w; a.side[s].blend_bias = h.blend_bias; a.side[s].o = h.out;
     a.side[s].rot = h.rot; a.side[s].betas = h.betas; a.side[s].cam_wp = h.cam_wp;
   }
   if (n_sides == 1) a.side[1] = a.side[0];
   a.K = K; a.ld_betas = ld_betas; a.B = B; a.img_res = img_res; a.min_s = min_s;
-  const int nb = (B + MH - 1) / MH;
-  // split the 13 vertex chunks over blockIdx.z until ~800 blocks (3 per CU) exist; only the splits that lower the
-  // largest per-block chunk count are candidates (results do not depend on the split).  Measured at 2048 hands:
-  // 4 -> 55 us, 7 -> 49 us, 13 -> 55 us; at 512 hands 13 is best (22 us)
-  const int base = nb * n_sides;
-  const int want = (800 + base - 1) / base;
-  int vs = NCHUNK;
-  const int cand[7] = {1, 2, 3, 4, 5, 7, 13};
-  for (int i = 6; i >= 0; --i)
-    if (cand[i] >= want) vs = cand[i];
-  a.vsplit = vs;
+  const int nb = (int)(((long long)B + MH - 1) / MH);
+  a.vsplit = hands_mano_heads_vsplit(B, n_sides);
   dim3 grid((unsigned)nb, (unsigned)n_sides, (unsigned)a.vsplit);
   if (axis_angle_input) hipLaunchKernelGGL(mano_heads_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(mano_heads_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a);
@@ -613,6 +620,7 @@ int hands_mano_skin_f32(const hands_mano_consts* c, const float* v_posed, int ld
       !out->vertices || !out->joints3d || !out->v3d_cam || !out->j3d_cam || !out->j2d_norm ||
       !out->cam_t || B <= 0 || ld_vp < NV * 3)
     return HANDS_EINVAL;
+  if ((uintptr_t)c->lbs_weights & 15u) return HANDS_EINVAL;      // the kernel loads a vertex's 16 weights 16 bytes wide
   hipLaunchKernelGGL(mano_skin_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, *c, v_posed, ld_vp, A,
                      joints16, cam_wp, K, img_res, min_s, *out, B);
   HANDS_LAUNCH_CHECK();

@@ -382,6 +382,21 @@ int hands_grasp_input_f32(const float* shape, int ld_shape, const float* rotmat,
  *                              (the 778x3 x 145 contraction on MFMA), output (B, ld_vp).
  *   3. hands_mano_skin_f32     per-vertex blend of A, apply, fingertip joints, weak-perspective
  *                              camera, K-projection, 2x/res-1 normalisation.
+ *
+ * Contract of the four MANO entries (hands_mano_pose_f32, hands_mano_pose_aa_f32, hands_mano_skin_f32,
+ * hands_mano_heads_f32; tests/test_gpu_mano_edges.py).  Every array is dense fp32 except the rows with a stride:
+ * betas (B, ld_betas >= 10), blend_in (B, ld_blend >= 145; the pose entries write columns [0,145) and ZERO
+ * columns [145, ld_blend)), v_posed (B, ld_vp >= 2334; columns past 2334 are not read).  K is (B,3,3) row-major
+ * and general: the projection is (K X)_xy / (K X)_z.  tip_ids are five vertex indices in [0, 778), not checked.
+ * Alignment: 4 bytes everywhere except
+ *   - hands_mano_skin_f32:  consts.lbs_weights 16 bytes (a vertex's 16 weights are four 16-byte loads);
+ *   - hands_mano_heads_f32: out.vertices and out.v3d_cam 8 bytes (stored two floats at a time; a hand's 2334
+ *                           floats keep that alignment from row to row), blend_w 16 bytes (16-byte loads).
+ * HANDS_EINVAL (nothing launched): a NULL pointer -- argument, descriptor or any member the entry reads (the pose
+ * entries: pose_mean, J_template, J_shapedirs; the skin entry: lbs_weights, tip_ids and the six outputs; the fused
+ * entry: all five constants, blend_w, blend_bias, rot, betas, cam_wp and the six outputs of every side) --,
+ * B <= 0, ld_betas < 10, ld_blend < 145, ld_vp < 2334, n_sides outside {1, 2}, or a pointer that misses the
+ * alignment above.
  * --------------------------------------------------------------------------------------------- */
 typedef struct hands_mano_consts {
   const float* pose_mean;   /* (48)      zeros(3) ++ hands_mean(45) */
@@ -428,6 +443,10 @@ typedef struct hands_mano_side {
 
 int hands_mano_heads_f32(const hands_mano_side* sides, int n_sides, const float* K, int ld_betas,
                          float img_res, float min_s, int B, int axis_angle_input, hands_stream_t stream);
+/* The number of blockIdx.z slices hands_mano_heads_f32 cuts the 13 chunks of 64 vertices into for (B, n_sides): one of
+ * {1, 2, 3, 4, 5, 7, 13}, the smallest that yields ~800 workgroups (slice z owns chunks [13 z / n, 13 (z + 1) / n));
+ * 0 for B <= 0 or n_sides outside {1, 2}.  A pure function (no device access); no output bit depends on it. */
+int hands_mano_heads_vsplit(int B, int n_sides);
 
 /* ---------------------------------------------------------------------------------------------
  * hamer_light (ViT-H/16 + cross-attention decoder head): src/models/hamer_light/.

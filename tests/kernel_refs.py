@@ -1,7 +1,8 @@
 """Plain float64 restatements of the non-convolution kernels of csrc/handocc.hip, csrc/transformer.hip, csrc/vit_b.hip,
 csrc/metrics.hip and csrc/elementwise.hip, for tests/test_gpu_kernel_edges.py and tests/test_gpu_io_edges.py (csrc/frontend.hip
-has its restatement in oracle/frontend_oracle.py), and -- last in the file -- ``conv_ref``, the one restatement of the convolution
-entry points of csrc/conv_igemm.hip on flat, strided buffers for tests/test_gpu_conv_edges.py.
+has its restatement in oracle/frontend_oracle.py), ``mano_head_ref`` (the MANO head of csrc/mano_lbs.hip with a general K, free
+tip vertices and min_s, for tests/test_gpu_mano_edges.py), and -- last in the file -- ``conv_ref``, the one restatement of the
+convolution entry points of csrc/conv_igemm.hip on flat, strided buffers for tests/test_gpu_conv_edges.py.
 
 One function per C entry point of include/hands_hip.h, named after it without ``hands_`` and ``_f32``.  Each takes the entry
 point's arguments in its order -- CPU tensors where the C function takes pointers, with the same layouts (NHWC maps, token rows,
@@ -13,6 +14,7 @@ function receives.  Where oracle/ already states an operation (the gated attenti
 not re-derived.  tests/test_kernel_refs.py pins every function here to the ATen operator or oracle function it restates;
 nothing here is imported by the package.
 """
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -412,6 +414,66 @@ def gt_targets(joints, verts, j3d_full, K, img_res, B, NV):
 
 def unnormalize_kp2d(x, n, img_res):
     return 0.5 * _f32(img_res) * (_d(x).reshape(-1)[:n] + 1)
+
+
+# ---- csrc/mano_lbs.hip ------------------------------------------------------------------------------------------------------
+def mano_head_ref(rot_or_aa, betas, cam, K, asset, img_res, min_s, tip_ids=O.TIP_IDS, aa_input=False):
+    """hands_mano_heads_f32 / the chain hands_mano_pose[_aa]_f32 -> blend GEMM -> hands_mano_skin_f32 for one side:
+    oracle.hands_oracle.mano_head and mano_lbs restated statement for statement (the same ATen calls in the same order, so the
+    float32 evaluation has the oracle's bits) with the three things the oracle fixes made free: a general (B, 3, 3) K -- the
+    projection is (K X)_xy / (K X)_z --, any five ``tip_ids``, any ``min_s``.  ``rot_or_aa``: (B, 16, 3, 3) rotation matrices, or
+    (B, 48) axis-angle with ``aa_input``.  ``img_res`` and ``min_s`` are used as given: pass the float32 values the C function
+    receives.  -> dict of the six outputs under the head's names plus the intermediates of the three-launch chain:
+    ``blend_row`` (B, 145) = [beta | R - I of joints 1..15], ``A`` (B, 16, 12) skinning transforms (3 x 4, row-major),
+    ``joints16`` (B, 16, 3) posed joints, and ``hz`` (B, 21), the third row of K X the projection divides by."""
+    dt = _DT
+    t = lambda a: torch.as_tensor(np.asarray(a)).to(dt)
+    betas, cam, K = _d(betas), _d(cam), _d(K)
+    B = betas.shape[0]
+    if aa_input:
+        aa = _d(rot_or_aa).reshape(B, 48)
+    else:
+        aa = O.matrix_to_axis_angle(_d(rot_or_aa).reshape(-1, 3, 3)).reshape(-1, 48)
+    global_orient, hand_pose = aa[:, :3], aa[:, 3:]
+    # smplx.MANO.forward as oracle.hands_oracle.mano_lbs states it
+    v_template, shapedirs, posedirs = t(asset.v_template), t(asset.shapedirs), t(asset.posedirs)
+    J_regressor, lbs_weights = t(asset.J_regressor), t(asset.lbs_weights)
+    pose_mean = torch.cat([torch.zeros(3, dtype=dt), t(asset.hands_mean)])
+    full_pose = torch.cat([global_orient, hand_pose], dim=1) + pose_mean
+    v_shaped = v_template + torch.einsum("bl,mkl->bmk", betas, shapedirs)
+    J = torch.einsum("bik,ji->bjk", v_shaped, J_regressor)
+    rot_mats = O.batch_rodrigues(full_pose.reshape(-1, 3)).view(B, 16, 3, 3)
+    pose_feature = (rot_mats[:, 1:] - torch.eye(3, dtype=dt)).reshape(B, -1)
+    v_posed = v_shaped + torch.matmul(pose_feature, posedirs).view(B, -1, 3)
+    rel_J = J.clone()
+    parents = list(O.PARENTS)
+    rel_J[:, 1:] = J[:, 1:] - J[:, parents[1:]]
+    T = torch.zeros(B, 16, 4, 4, dtype=dt)
+    T[:, :, :3, :3] = rot_mats
+    T[:, :, :3, 3] = rel_J
+    T[:, :, 3, 3] = 1
+    chain = [T[:, 0]]
+    for i in range(1, 16):
+        chain.append(torch.matmul(chain[parents[i]], T[:, i]))
+    G = torch.stack(chain, dim=1)
+    posed_joints = G[:, :, :3, 3]
+    J_h = torch.cat([J, torch.zeros(B, 16, 1, dtype=dt)], dim=2)[..., None]
+    A = G.clone()
+    A[:, :, :, 3] = G[:, :, :, 3] - torch.matmul(G, J_h)[..., 0]
+    Tv = torch.matmul(lbs_weights[None].expand(B, -1, -1), A.view(B, 16, 16)).view(B, -1, 4, 4)
+    v_h = torch.cat([v_posed, torch.ones(B, v_posed.shape[1], 1, dtype=dt)], dim=2)
+    verts = torch.matmul(Tv, v_h[..., None])[:, :, :3, 0]
+    joints = torch.cat([posed_joints, verts[:, list(tip_ids)]], dim=1)
+    # MANOHead.forward as oracle.hands_oracle.mano_head states it
+    avg_f = (K[:, 0, 0] + K[:, 1, 1]) / 2.0
+    cam_t = O.weak_perspective_to_perspective(cam, avg_f, img_res, min_s)
+    j3d_cam = joints + cam_t[:, None, :]
+    v3d_cam = verts + cam_t[:, None, :]
+    homo = torch.bmm(K, j3d_cam.permute(0, 2, 1)).permute(0, 2, 1)
+    j2d = O.normalize_kp2d(homo[:, :, :2] / homo[:, :, 2:3], img_res)
+    return {"vertices": verts, "joints3d": joints, "v3d.cam": v3d_cam, "j3d.cam": j3d_cam, "j2d.norm": j2d, "cam_t": cam_t,
+            "blend_row": torch.cat([betas, pose_feature], dim=1), "A": A[:, :, :3, :].reshape(B, 16, 12).clone(),
+            "joints16": posed_joints.clone(), "hz": homo[:, :, 2].clone()}
 
 
 # ---- csrc/conv_igemm.hip ----------------------------------------------------------------------------------------------------

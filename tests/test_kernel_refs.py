@@ -506,3 +506,75 @@ def test_conv_ref_against_aten(B, Cin, H, W, Cout, KH, KW, stride, pad, act):
         s = s + _nchw(r.float().view(B, d.Ho, d.Wo, Cout))
         s = {0: lambda t: t, 1: F.relu, 3: lambda t: F.leaky_relu(t, 0.01)}[act](s)
         assert (_nchw(rs.view(B, d.Ho, d.Wo, Cout)) != s.double()).float().mean().item() < 1e-3      # ties of the fp64 sum's order only
+
+
+# ---- mano_head_ref ----------------------------------------------------------------------------------------------------------
+def _mano_assets():
+    import fake_mano
+    import hands_amd
+    import mano_cases as MC
+    return [hands_amd.synthetic_mano_asset(True), hands_amd.synthetic_mano_asset(False), fake_mano.realistic_mano_asset(True),
+            MC.dense_weight_asset(False)]
+
+
+@pytest.mark.parametrize("which", [0, 1, 2, 3])
+def test_mano_head_ref_is_the_oracle_at_the_oracles_parameters(which):
+    """Default tips, K = diag(f, f, 1) with a principal point, min_s = 0.1: the oracle's numbers exactly in float64, and the
+    oracle's bits at the float32 switch (the same ATen calls in the same order)."""
+    import mano_cases as MC
+    asset = _mano_assets()[which]
+    rot, aa, betas, cam, _ = MC.inputs(7, 40 + which, sigma=1.0 + which)
+    cam[2, 0] = -0.5                                                       # the clamp
+    g = torch.Generator().manual_seed(which)
+    K = torch.tensor([[1000.0, 0, 112], [0, 1000.0, 112], [0, 0, 1]])[None].repeat(7, 1, 1)
+    K[:, 0, 0] += 20 * torch.randn(7, generator=g)
+    keys = ("vertices", "joints3d", "v3d.cam", "j3d.cam", "j2d.norm", "cam_t")
+    want64 = O.mano_head(rot.double(), betas.double(), cam.double(), K.double(), asset, 224, "")
+    got64 = R.mano_head_ref(rot, betas, cam, K, asset, 224, 0.1)
+    for k in keys:
+        assert got64[k].dtype == torch.float64 and torch.equal(got64[k], want64[k]), k
+    want32 = O.mano_head(rot, betas, cam, K, asset, 224, "")
+    with R.precision(torch.float32):
+        got32 = R.mano_head_ref(rot, betas, cam, K, asset, 224, 0.1)
+    for k in keys:
+        assert got32[k].dtype == torch.float32 and torch.equal(got32[k], want32[k]), k
+    v64, j64 = O.mano_lbs(betas, aa[:, :3], aa[:, 3:], asset, dtype=torch.float64)
+    via_aa = R.mano_head_ref(aa, betas, cam, K, asset, 224, 0.1, aa_input=True)
+    assert torch.equal(via_aa["vertices"], v64) and torch.equal(via_aa["joints3d"], j64)
+    # the intermediates: joints16 are the first 16 joints; A applied through the weights gives the vertices back
+    assert torch.equal(got64["joints16"], got64["joints3d"][:, :16]) and got64["A"].shape == (7, 16, 12)
+    assert got64["blend_row"].shape == (7, 145) and torch.equal(got64["blend_row"][:, :10], betas.double())
+    vp = torch.from_numpy(asset.v_template).double() + torch.cat([got64["blend_row"][:, :10] @ torch.from_numpy(
+        asset.shapedirs).double().reshape(-1, 10).t()], 1).view(7, 778, 3) + (got64["blend_row"][:, 10:] @ torch.from_numpy(
+            asset.posedirs).double()).view(7, 778, 3)
+    Tv = torch.einsum("vj,bje->bve", torch.from_numpy(asset.lbs_weights).double(), got64["A"]).view(7, 778, 3, 4)
+    again = torch.einsum("bvij,bvj->bvi", Tv[..., :3], vp) + Tv[..., 3]
+    assert (again - got64["vertices"]).abs().max().item() < F64
+
+
+@pytest.mark.parametrize("which,min_s,img_res", [(0, 0.25, 256.0), (2, 0.1, 192.5), (3, 0.25, 224.0)])
+def test_mano_head_ref_general_K_and_tips_against_per_vertex_loops(which, min_s, img_res):
+    """The parameters tests/test_gpu_mano_edges.py frees -- a general K, tips at chunk edges, min_s -- against the loop-written
+    evaluation of mano_cases.mano_head_loops: vertices[tips], K @ X, the division by row 2, element by element."""
+    import mano_cases as MC
+    asset = _mano_assets()[which]
+    rot, aa, betas, cam, K = MC.inputs(5, 50 + which, sigma=3.0)
+    cam[0, 0], cam[1, 0], cam[4, 0] = min_s, -0.5, 3.0
+    got = R.mano_head_ref(aa, betas, cam, K, asset, img_res, min_s, tip_ids=MC.EDGE_TIPS, aa_input=True)
+    want = MC.mano_head_loops(aa, betas, cam, K, asset, img_res, min_s, MC.EDGE_TIPS)
+    assert got["hz"].min().item() > 1.0 and (K[:, 2, :2].abs() > 5e-4).all() and (K[:, 0, 1] != K[:, 1, 0]).all()
+    for k, tol in (("vertices", 1e-13), ("joints3d", 1e-13), ("j3d.cam", 1e-12), ("cam_t", 1e-12), ("j2d.norm", 1e-11)):
+        err = (got[k] - want[k]).abs().max().item()
+        assert err < tol, (k, err)
+    assert torch.equal(got["joints3d"][:, 16:], got["vertices"][:, list(MC.EDGE_TIPS)])
+    # matrix input: the loops on the axis-angle rows the reference's conversion makes of the matrices (a quaternion that is not
+    # standardised: an angle above pi where a vector component outweighs w, so NOT the rows the matrices were made from)
+    via_rot = R.mano_head_ref(rot, betas, cam, K, asset, img_res, min_s, tip_ids=MC.EDGE_TIPS)
+    aa2 = O.matrix_to_axis_angle(rot.double().reshape(-1, 3, 3)).reshape(5, 48)
+    want2 = MC.mano_head_loops(aa2, betas, cam, K, asset, img_res, min_s, MC.EDGE_TIPS)
+    assert (via_rot["vertices"] - want2["vertices"]).abs().max().item() < 1e-13
+    assert (via_rot["j2d.norm"] - want2["j2d.norm"]).abs().max().item() < 1e-11
+    # a projection that ignored the last row, or the skew, would be far off
+    naive = (got["j3d.cam"][..., :2] * torch.stack([K[:, 0, 0], K[:, 1, 1]], -1).double()[:, None] / got["j3d.cam"][..., 2:]
+             + K[:, :2, 2].double()[:, None])
+    assert (2 * naive / img_res - 1 - got["j2d.norm"]).abs().max().item() > 1e-3
