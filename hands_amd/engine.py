@@ -369,6 +369,23 @@ class _GroupPC:
 DEFAULT_ENGINE = ConvEngine()
 
 
+def linear_chain(engine, L, layers, x, rows, stream, buf, names, out=None, in_ps=None, x_off=0, out_ps=None, out_off=0):
+    """A chain of linear layers on ``rows`` per-sample rows, one :meth:`ConvEngine.conv` launch each: ``layers`` is a list of
+    ``(pc, act, splitk)``.  Layer i writes ``buf(names[i], rows * pc.Cout)`` from the caller's workspace allocator -- names that
+    are live on two streams at once must differ -- and the last layer ``out`` when one is given (``names`` may then be one
+    short).  ``in_ps`` / ``x_off`` describe the first layer's input rows, ``out_ps`` / ``out_off`` the last layer's output rows.
+    Returns the last output."""
+    last = len(layers) - 1
+    for i, (pc, act, splitk) in enumerate(layers):
+        y = out if (i == last and out is not None) else buf(names[i], rows * pc.Cout)
+        kw = {"in_ps": in_ps, "x_off": x_off} if i == 0 else {}
+        if i == last:
+            kw.update(out_ps=out_ps, out_off=out_off)
+        engine.conv(L, pc, x, rows, 1, 1, y, act, stream, splitk=splitk, **kw)
+        x = y
+    return x
+
+
 class EngineSwitches:
     """Mixin: per-instance views of the engine switches under the names the models always used."""
 

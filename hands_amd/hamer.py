@@ -30,13 +30,14 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import ACT_GELU, ACT_NONE, ACT_RELU, check, ptr
-from .engine import ConvEngine, EngineSwitches
-from .mano_head import MANOHead, pack_mano_pair, run_mano_heads
-from .packing import hmr_decoder_rows, pack_conv, pack_linear
-from .streams import SideJobs
+from .engine import ConvEngine, EngineSwitches, linear_chain
+from .grasp_head import GRASP_SPLITK, pack_grasp_head, run_grasp_head
+from .mano_head import MANOHead, pack_mano_pair, run_mano_heads_from_pred
+from .packing import pack_conv, pack_hmr_decoders, pack_linear
+from .streams import run_crop_chunks
 from .vit_encoder import vit_encoder_blocks
 from .weights import synthetic_mano_mean_params
-from .xdict import _Args, args_getter, xdict
+from .xdict import _Args, args_getter
 
 VIT_DIM, VIT_DEPTH, VIT_HEADS, VIT_HDIM = 1280, 32, 16, 80
 DEC_DIM, DEC_DEPTH, DEC_HEADS, DEC_HDIM = 1024, 6, 8, 64
@@ -273,18 +274,12 @@ class HAMER(EngineSwitches, nn.Module):
             + cpu(td.pos_embedding)[0, :1]
         P["tok0"] = tok0.to(dev)
         mh = self.mano_head
-        wd = torch.cat([cpu(mh.decpose.weight), cpu(mh.decshape.weight), cpu(mh.deccam.weight)], 0)
-        bd = torch.cat([cpu(mh.decpose.bias), cpu(mh.decshape.bias), cpu(mh.deccam.bias)], 0)
-        P["decout"] = pack_linear(wd, bd, dev, row_index=hmr_decoder_rows(), n_total=112)
+        P["decout"] = pack_hmr_decoders(*[(m.weight, m.bias) for m in (mh.decpose, mh.decshape, mh.deccam)], dev)
         init = torch.zeros(112)
         init[:96], init[96:106], init[108:111] = cpu(mh.init_hand_pose)[0], cpu(mh.init_betas)[0], cpu(mh.init_cam)[0]
         P["init"] = init.to(dev)
         if self.use_grasp_loss:
-            g = self.grasp_classifier
-            gcol = [144 + i for i in range(10)] + list(range(144))          # reference cat([shape, pose])
-            P["g0"] = pack_linear(cpu(g[0].weight), cpu(g[0].bias), dev, col_index=gcol, k_total=154)
-            P["g2"], P["g4"] = lin(g[2]), lin(g[4])
-            P["g6"] = lin(g[6], n_total=12)
+            P["grasp"] = pack_grasp_head(self.grasp_classifier[0::2], dev)
         P["mano_r"], P["mano_l"] = pack_mano_pair(self.mano_r, self.mano_l, dev)
         return P
 
@@ -324,11 +319,6 @@ class HAMER(EngineSwitches, nn.Module):
         P = self.packed(dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
         buf = lambda n, numel: self._buf(n, numel, dev)
-        gemm = lambda pc, x, rows, out, act=ACT_NONE, **kw: self.engine.conv(L, pc, x, rows, 1, 1, out, act, stream, **kw)
-        hgemm = lambda *a, **kw: gemm(*a, splitk=True, **kw)     # per-sample rows: latency-bound head GEMMs
-        lnorm = lambda x, gb, out, rows, Cc, eps, addvec=None, rpv=1: check(
-            L.hands_layernorm_f32(ptr(x), ptr(gb[0]), ptr(gb[1]), ptr(out), ptr(addvec), rpv, rows, Cc, eps, stream),
-            "layernorm")
 
         # -- model.py:82-100: resize to 256x256, cat(r,l), keep columns 32..223 -> NHWC4 ----------
         S, Wc = max(self.vit_input_size), min(self.vit_input_size)
@@ -342,10 +332,10 @@ class HAMER(EngineSwitches, nn.Module):
             center = torch.cat([f32(inputs["r_center_angle"]), f32(inputs["l_center_angle"])], 0)
             corner = torch.cat([f32(inputs["r_corner_angle"]), f32(inputs["l_corner_angle"])], 0)
             kld = P["kpe0"].Cin
-            enc, k1, kpe = buf("kpe_enc", B2 * kld), buf("kpe_h", B2 * Cd), buf("kpe", B2 * Cd)
+            enc = buf("kpe_enc", B2 * kld)
             check(L.hands_kpe_encode_f32(ptr(center), ptr(corner), ptr(enc), B2, kld, self.n_freq, stream), "kpe_encode")
-            hgemm(P["kpe0"], enc, B2, k1, ACT_RELU)
-            hgemm(P["kpe2"], k1, B2, kpe, ACT_RELU)
+            kpe = linear_chain(self.engine, L, [(P["kpe0"], ACT_RELU, True), (P["kpe2"], ACT_RELU, True)], enc, B2, stream, buf,
+                               ("kpe_h", "kpe"))
         # -- ViT-H/16 + decoder head, per chunk of crops -----------------------------------------------
         pred = torch.empty(B2, 112, device=dev)
         inner = DEC_HEADS * DEC_HDIM
@@ -360,7 +350,7 @@ class HAMER(EngineSwitches, nn.Module):
             Mc = nB * T
             cbuf = lambda n, numel: self._buf(f"{n}@{tag}", numel, dev)
             gemm = lambda pc, x, rows, out, act=ACT_NONE, **kw: self.engine.conv(L, pc, x, rows, 1, 1, out, act, sh, **kw)
-            hgemm = lambda *a, **kw: gemm(*a, splitk=True, **kw)
+            hgemm = lambda *a, **kw: gemm(*a, splitk=True, **kw)     # per-sample rows: latency-bound head GEMMs
             lnorm = lambda x, gb, out, rows, Cc, eps, addvec=None, rpv=1: check(
                 L.hands_layernorm_f32(ptr(x), ptr(gb[0]), ptr(gb[1]), ptr(out), addvec, rpv, rows, Cc, eps, sh), "layernorm")
             # ViT-H/16 (vit.py:320-342)
@@ -394,41 +384,12 @@ class HAMER(EngineSwitches, nn.Module):
 
         main = torch.cuda.current_stream(dev)
         nch = self.chunks if self.engine.overlap else 1
-        nch = max(1, min(nch, B2))
-        if nch == 1:
-            pipeline(0, B2, main, "c0")
-        else:
-            chunks = SideJobs(main)
-            for ci in range(nch):
-                lo, hi = ci * B2 // nch, (ci + 1) * B2 // nch
-                st = main if ci == nch - 1 else self._side_stream(dev, ci)
-                chunks.begin(st)
-                with torch.cuda.stream(st):
-                    pipeline(lo, hi - lo, st, f"c{ci}")
-                chunks.end(st)
-            chunks.join()
-        rot = torch.empty(B2, 16, 3, 3, device=dev)
-        check(L.hands_rot6d_to_matrix_cols_f32(ptr(pred), 112, ptr(rot), B2, stream), "rot6d_cols")
-        shape = pred[:, 96:106].contiguous()
-        cam = pred[:, 108:111].contiguous()
-        # -- MANOHead x2 (model.py:125-129) ----------------------------------------------------------
-        output = run_mano_heads(L, P["mano_r"], P["mano_l"], rot, shape, cam, cam, K, float(self.img_res), bz,
-                                stream, buf, self.engine)
+        run_crop_chunks(main, max(1, min(nch, B2)), B2, lambda ci: self._side_stream(dev, ci),
+                        lambda lo, hi, st, ci: pipeline(lo, hi - lo, st, f"c{ci}"))
+        # -- rot6d, MANOHead x2 (model.py:125-129) ---------------------------------------------------
+        output, rot, shape = run_mano_heads_from_pred(L, P["mano_r"], P["mano_l"], pred, K, float(self.img_res), bz, stream, buf,
+                                                      self.engine)
         # -- grasp classifier (model.py:136-143) -----------------------------------------------------
-        if not self.use_grasp_loss:
-            return output
-        gld = P["g0"].Cin
-        gin = buf("grasp_in", B2 * gld)
-        check(L.hands_grasp_input_f32(ptr(shape), 10, ptr(rot), ptr(shape), ptr(gin), B2, bz, 0, gld, stream),
-              "grasp_input")
-        g1, g2, g3 = buf("g1", B2 * 1024), buf("g2", B2 * 512), buf("g3", B2 * 128)
-        g4 = torch.empty(B2, 12, device=dev)
-        hgemm(P["g0"], gin, B2, g1, ACT_RELU)
-        hgemm(P["g2"], g1, B2, g2, ACT_RELU)
-        hgemm(P["g4"], g2, B2, g3, ACT_RELU)
-        hgemm(P["g6"], g3, B2, g4)
-        grasp = xdict()
-        grasp["grasp.r"] = g4[:bz, :9].contiguous()
-        grasp["grasp.l"] = g4[bz:, :9].contiguous()
-        output.merge(grasp)
+        if self.use_grasp_loss:
+            output.merge(run_grasp_head(self.engine, L, P["grasp"], GRASP_SPLITK["hamer"], shape, rot, bz, stream, buf))
         return output

@@ -24,12 +24,13 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import ACT_GELU, ACT_LEAKY_RELU, ACT_NONE, ACT_RELU, check, ptr
-from .engine import ConvEngine, EngineSwitches
-from .mano_head import MANOHead, pack_mano_pair, run_mano_heads
-from .packing import BN_EPS, PackedConv, fold_bn, hmr_decoder_rows, pack_conv, pack_linear
+from .engine import ConvEngine, EngineSwitches, linear_chain
+from .grasp_head import GRASP_SPLITK, pack_grasp_head, run_grasp_head
+from .mano_head import MANOHead, pack_mano_pair, run_mano_heads_from_pred
+from .packing import BN_EPS, PackedConv, fold_bn, pack_conv, pack_hmr_decoders, pack_linear
 from .param_tree import build_tree, load_manifest
-from .streams import SideJobs
-from .xdict import _Args, args_getter, stream_xdict, xdict
+from .streams import run_crop_chunks
+from .xdict import _Args, args_getter, stream_xdict
 
 HANDOCC_DEFAULT_ARGS = _Args(pos_enc="center+corner_latent", n_freq_pos_enc=4, use_grasp_loss=True,
                              use_render_seg_loss=False, img_res=224, focal_length=1000.0,
@@ -57,8 +58,8 @@ def stage_of(p: str) -> str:
     return "mlp"                           # mano_head.py:190-207, the KPE MLP, the grasp classifier
 
 
-def _conv_fns(L, stream, new, engine, small_map_splitk=True):
-    """(conv, hconv) launchers bound to one HIP stream; hconv = per-sample rows (split-K head GEMMs)."""
+def _conv_fn(L, stream, new, engine, small_map_splitk=True):
+    """The layer launcher bound to one HIP stream (it allocates the output)."""
     def conv(pc: PackedConv, x, B, H, W, act=ACT_NONE, res=None, out=None, **kw):
         Ho = (H + 2 * pc.pad - pc.KH) // pc.stride + 1
         Wo = (W + 2 * pc.pad - pc.KW) // pc.stride + 1
@@ -75,7 +76,7 @@ def _conv_fns(L, stream, new, engine, small_map_splitk=True):
         engine.conv(L, pc, x, B, H, W, out, act, stream, res=res, **kw)
         return out, Ho, Wo
 
-    return conv, (lambda *a, **kw: conv(*a, splitk=True, **kw))
+    return conv
 
 
 class HandOccNet(EngineSwitches, nn.Module):
@@ -134,7 +135,7 @@ class HandOccNet(EngineSwitches, nn.Module):
                                            # 10-20x F(2x2)'s per-layer rounding: off -- tools/hon_parity_ab.py arm "+w4:resnet")
         self.acc64_3x3 = True              # False: the 3x3 layers of the fp64 stages keep their fp32 route (Winograd / blocked direct)
         self.small_map_splitk = False  # True / "deep" / "16x16": call-site constant split-K on maps of <= 8x8 pixels and on the
-                                       # one-tile 16x16 layers (see _conv_fns).  Off since round 5: with three forwards in flight the
+                                       # one-tile 16x16 layers (see _conv_fn).  Off since round 5: with three forwards in flight the
                                        # chip is filled by other forwards, and the reduce launches cost more than the slices gain
                                        # (tools/experiments/ab_small_map_splitk.py: +2.3 % at 32 samples, +2.9 % at 256); True shortens ONE
                                        # synchronous forward at 2 samples by 6 % (6.5 against 6.9 ms)
@@ -265,15 +266,10 @@ class HandOccNet(EngineSwitches, nn.Module):
         col = [(k % 4) * 256 + (k // 4) for k in range(1024)]
         P["base0"] = lin(mp + ".mano_base_layer.0", col_index=col)
         P["base2"] = lin(mp + ".mano_base_layer.2")
-        wd = torch.cat([sd[mp + ".pose_reg.weight"], sd[mp + ".shape_reg.weight"], sd[mp + ".cam_reg.weight"]], 0)
-        bd = torch.cat([sd[mp + ".pose_reg.bias"], sd[mp + ".shape_reg.bias"], sd[mp + ".cam_reg.bias"]], 0)
-        P["regs"] = pack_linear(wd, bd, dev, row_index=hmr_decoder_rows(), n_total=112)
+        P["regs"] = pack_hmr_decoders(*[(sd[f"{mp}.{n}_reg.weight"], sd[f"{mp}.{n}_reg.bias"]) for n in ("pose", "shape", "cam")], dev)
         P["regs"].acc64 = "mlp" in self.acc64_stages
         if self.use_grasp_loss:
-            gcol = [144 + i for i in range(10)] + list(range(144))
-            P["g0"] = lin("grasp_classifier.0", col_index=gcol, k_total=154)
-            P["g2"], P["g4"] = lin("grasp_classifier.2"), lin("grasp_classifier.4")
-            P["g6"] = lin("grasp_classifier.6", n_total=12)
+            P["grasp"] = pack_grasp_head([f"grasp_classifier.{i}" for i in (0, 2, 4, 6)], dev, lin=lin)
         P["mano_r"], P["mano_l"] = pack_mano_pair(self.mano_r, self.mano_l, dev)
         return P
 
@@ -346,14 +342,13 @@ class HandOccNet(EngineSwitches, nn.Module):
         B2, S = 2 * bz, 256
         stream = torch.cuda.current_stream(dev).cuda_stream
         new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
-
-        conv, hconv = _conv_fns(L, stream, new, self.engine, self.small_map_splitk)
+        fresh = lambda name, numel: new(numel)     # the `buf(name, numel)` of linear_chain: every activation is allocated per call
 
         def pipeline(x4, center, corner, B2, stream):
             """Everything per crop, from the NHWC image to the 112-vector of the regressor; rows are
             independent, so the 2*bz crops may be cut into chunks that run on separate HIP streams."""
             npix = B2 * NTOK
-            conv, hconv = _conv_fns(L, stream, new, self.engine, self.small_map_splitk)
+            conv = _conv_fn(L, stream, new, self.engine, self.small_map_splitk)
 
             def group(*jobs):
                 """Independent layers (pc, x, B, H, W[, act[, res[, pre]]]) -> their outputs; pointwise ones of one kernel class
@@ -378,9 +373,8 @@ class HandOccNet(EngineSwitches, nn.Module):
             if self.pos_enc is not None:
                 enc = new(B2, P["kpe0"].Cin)
                 check(L.hands_kpe_encode_f32(ptr(center), ptr(corner), ptr(enc), B2, P["kpe0"].Cin, self.n_freq, stream), "kpe")
-                k1, _, _ = conv(P["kpe0"], enc, B2, 1, 1, ACT_RELU)
-                kpe, _, _ = conv(P["kpe2"], k1, B2, 1, 1, ACT_RELU)
-                kpe = kpe.view(B2, CF)
+                kpe = linear_chain(self.engine, L, [(P["kpe0"], ACT_RELU, False), (P["kpe2"], ACT_RELU, False)], enc, B2, stream, fresh,
+                                   ("kpe_h", "kpe")).view(B2, CF)
             else:
                 # pos_enc None (model.py:74-89: no KPE term anywhere): a zero vector through the same kernels -- x + 0 == x
                 kpe = torch.zeros(B2, CF, dtype=torch.float32, device=dev)
@@ -536,10 +530,9 @@ class HandOccNet(EngineSwitches, nn.Module):
                 H, W = H // 2, W // 2
             if dbg is not None:
                 dbg["enc"] = x
-            f = hconv(P["base0"], x, B2, 1, 1, ACT_LEAKY_RELU)[0]         # x: (B2,2,2,256) read as (B2,1024)
-            f = hconv(P["base2"], f, B2, 1, 1, ACT_LEAKY_RELU)[0]
-            pred = hconv(P["regs"], f, B2, 1, 1)[0].view(B2, 112)
-            return pred
+            # x: (B2,2,2,256) read as (B2,1024)
+            return linear_chain(self.engine, L, [(P["base0"], ACT_LEAKY_RELU, True), (P["base2"], ACT_LEAKY_RELU, True),
+                                                 (P["regs"], ACT_NONE, True)], x, B2, stream, fresh, ("base0", "base2", "pred")).view(B2, 112)
 
         dbg = self.__dict__.get("_debug")
         main = torch.cuda.current_stream(dev)
@@ -549,51 +542,22 @@ class HandOccNet(EngineSwitches, nn.Module):
         # forward is 0.6-1.4 % faster at 512 crops -- the crop jobs are for a forward that runs alone
         nch = self.chunks if (dbg is None and self.engine.overlap and not pipelined
                               and (B2 >= 128 or self.engine.latency_mode)) else 1
-        nch = max(1, min(nch, B2))
-        if nch == 1:
-            pred = pipeline(x4, center, corner, B2, stream)
-        else:
-            # chunks of crops on separate streams: a launch is a few hundred workgroups on 256 CUs, and
-            # the other chunk's workgroups fill its tail (same idea as HandsLight.trunk_chunks)
-            chunks, parts = SideJobs(main), []
-            for ci in range(nch):
-                lo, hi = ci * B2 // nch, (ci + 1) * B2 // nch
-                st = main if ci == nch - 1 else self._side_stream(dev, ci)
-                chunks.begin(st)
-                with torch.cuda.stream(st):
-                    pc_ = pipeline(x4[lo:hi], center[lo:hi].contiguous(), corner[lo:hi].contiguous(), hi - lo, st.cuda_stream)
-                if st is not main:
-                    pc_.record_stream(main)
-                chunks.end(st)
-                parts.append(pc_)
-            chunks.join()
-            pred = torch.cat(parts, 0)
-        rot = new(B2, 16, 3, 3)
-        check(L.hands_rot6d_to_matrix_cols_f32(ptr(pred), 112, ptr(rot), B2, stream), "rot6d_cols")
+
+        def chunk(lo, hi, st, ci):
+            pc_ = pipeline(x4[lo:hi], center[lo:hi].contiguous(), corner[lo:hi].contiguous(), hi - lo, st.cuda_stream)
+            if st is not main:
+                pc_.record_stream(main)
+            return pc_
+
+        # chunks of crops on separate streams: a launch is a few hundred workgroups on 256 CUs, and
+        # the other chunk's workgroups fill its tail (same idea as HandsLight.trunk_chunks)
+        parts = run_crop_chunks(main, max(1, min(nch, B2)), B2, lambda ci: self._side_stream(dev, ci), chunk)
+        pred = parts[0] if len(parts) == 1 else torch.cat(parts, 0)
         if dbg is not None:
             dbg["pred"] = pred
-        shape = pred[:, 96:106].contiguous()
-        cam = pred[:, 108:111].contiguous()
-        # -- MANOHead x2, grasp (model.py:103-120) ------------------------------------------------------
-        ws = {}
-
-        def buf(name, numel):
-            if name not in ws:
-                ws[name] = new(numel)
-            return ws[name]
-
-        output = run_mano_heads(L, P["mano_r"], P["mano_l"], rot, shape, cam, cam, K, float(self.img_res), bz, stream, buf, self.engine)
-        if not self.use_grasp_loss:
-            return output
-        gld = P["g0"].Cin
-        gin = new(B2, gld)
-        check(L.hands_grasp_input_f32(ptr(shape), 10, ptr(rot), ptr(shape), ptr(gin), B2, bz, 0, gld, stream), "grasp_in")
-        g = hconv(P["g0"], gin, B2, 1, 1, ACT_RELU)[0]
-        g = hconv(P["g2"], g, B2, 1, 1, ACT_RELU)[0]
-        g = conv(P["g4"], g, B2, 1, 1, ACT_RELU)[0]
-        g4 = conv(P["g6"], g, B2, 1, 1)[0].view(B2, 12)
-        grasp = xdict()
-        grasp["grasp.r"] = g4[:bz, :9].contiguous()
-        grasp["grasp.l"] = g4[bz:, :9].contiguous()
-        output.merge(grasp)
+        # -- rot6d, MANOHead x2, grasp (model.py:103-120) -----------------------------------------------
+        output, rot, shape = run_mano_heads_from_pred(L, P["mano_r"], P["mano_l"], pred, K, float(self.img_res), bz, stream, fresh,
+                                                      self.engine)
+        if self.use_grasp_loss:
+            output.merge(run_grasp_head(self.engine, L, P["grasp"], GRASP_SPLITK["handoccnet"], shape, rot, bz, stream, fresh))
         return output

@@ -38,8 +38,9 @@ None (the reference itself fails on tf_decoder with 'sinusoidal_cc', 'cam_conv',
 backbone='resnet18' and the renderer switch raise ``NotImplementedError``.
 
 This file is the model: its defaults, constructor switches, packing and forward orchestration, workspaces and streams.  The
-trunks are ``resnet50.py`` / ``vit_b16.py``, the HandHMR, transformer and depth heads ``hmr_head.py``, the MANO head
-``mano_head.py``, the fork / join of side-stream jobs ``streams.py``.
+trunks are ``resnet50.py`` / ``vit_b16.py``, the HandHMR heads (iterative ``iter_head``, transformer ``tf_head``) and the depth
+head ``hmr_head.py``, the MANO head ``mano_head.py``, the grasp classifier ``grasp_head.py``, chains of per-sample linear
+layers ``engine.linear_chain``, the fork / join of side-stream jobs ``streams.py``.
 """
 from __future__ import annotations
 
@@ -48,8 +49,9 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import check, ptr
-from .engine import DEFAULT_ENGINE, ConvEngine, EngineSwitches
-from .hmr_head import TF_PASS, HandHMR, depth_head, pack_hmr_head, tf_head
+from .engine import DEFAULT_ENGINE, ConvEngine, EngineSwitches, linear_chain
+from .grasp_head import GRASP_SPLITK, pack_grasp_head, run_grasp_head
+from .hmr_head import TF_PASS, HandHMR, depth_head, iter_head, pack_hmr_head, tf_head
 from .mano_head import MANOHead, ManoHeadsPlan, pack_mano_pair, run_mano_heads  # noqa: F401  (ManoHeadsPlan: importable from here)
 from .packing import HMR_VEC, pack_conv, pack_linear
 from .resnet50 import ResNet50Params, pack_resnet50_trunk, resnet50_trunk
@@ -283,14 +285,7 @@ class HandsLight(EngineSwitches, nn.Module):
             col = [(k % 9) * 256 + (k // 9) for k in range(256 * 9)]
             P["fc7"] = pack_linear(cpu(fc[7].weight), cpu(fc[7].bias), dev, col_index=col)
         if self.use_grasp_loss:
-            g = self.grasp_classifier
-            Fg = F if self.use_glb_feat_w_grasp else 0
-            # reference cat([shape 10, rot 144(, feat_vec F)]) -> packed row [feat_vec F | rot 144 | shape 10]
-            gcol = [Fg + 144 + i for i in range(10)] + [Fg + i for i in range(144)] + list(range(Fg))
-            P["g0"] = pack_linear(cpu(g[0].weight), cpu(g[0].bias), dev, col_index=gcol, k_total=Fg + 154)
-            P["g2"] = pack_linear(cpu(g[2].weight), cpu(g[2].bias), dev)
-            P["g4"] = pack_linear(cpu(g[4].weight), cpu(g[4].bias), dev)
-            P["g6"] = pack_linear(cpu(g[6].weight), cpu(g[6].bias), dev, n_total=12)
+            P["grasp"] = pack_grasp_head(self.grasp_classifier[0::2], dev, F if self.use_glb_feat_w_grasp else 0)
         P["mano_r"], P["mano_l"] = pack_mano_pair(self.mano_r, self.mano_l, dev)
         return P
 
@@ -546,19 +541,7 @@ class HandsLight(EngineSwitches, nn.Module):
             if self.tf_decoder:
                 tf_head(self.engine, buf, L, hp, sh, side, bz, HW, cat, state, caminit4, F, cat_ld, self.tf_pass)
             else:
-                h512a, h512b = buf(f"h512a{side}", bz * 512), buf(f"h512b{side}", bz * 512)
-                x1, x2 = buf(f"x1024a{side}", bz * 1024), buf(f"x1024b{side}", bz * 1024)
-                so = side * bz * ld
-                self.engine.conv(L, hp["ci0"], state, bz, 1, 1, h512a, True, sh, in_ps=ld, x_off=so, splitk=True)
-                self.engine.conv(L, hp["ci2"], h512a, bz, 1, 1, h512b, True, sh, splitk=True)
-                self.engine.conv(L, hp["ci4"], h512b, bz, 1, 1, caminit4, False, sh, out_off=side * bz * 4)
-                check(L.hands_hmr_init_f32(ptr(state, so), ptr(caminit4, side * bz * 4), bz, ld, F, sh),
-                      "hmr_init")
-                for _ in range(3):
-                    self.engine.conv(L, hp["r0"], state, bz, 1, 1, x1, True, sh, in_ps=ld, x_off=so, splitk=True)
-                    self.engine.conv(L, hp["r3"], x1, bz, 1, 1, x2, True, sh, splitk=True)
-                    self.engine.conv(L, hp["dec"], x2, bz, 1, 1, state, False, sh, res=state, out_ps=ld,
-                               res_ps=ld, out_off=so + F, res_off=so + F, splitk=True)
+                iter_head(self.engine, buf, L, hp, sh, side, bz, state, caminit4, F)
             heads.end(hs)
         heads.join()
         rotmat = buf("rotmat", B2 * 144)
@@ -592,11 +575,9 @@ class HandsLight(EngineSwitches, nn.Module):
             extra = xdict()
             for nm, key in (("cc_center", "center"), ("cc_corner", "corner")):
                 l0, l1, l2 = P[nm]
-                h1, h2 = buf("cc_h1", B2 * 512), buf("cc_h2", B2 * 128)
                 o = torch.empty(B2, 8, device=dev)
-                self.engine.conv(L, l0, state, B2, 1, 1, h1, True, stream, in_ps=ld, splitk=True)
-                self.engine.conv(L, l1, h1, B2, 1, 1, h2, True, stream, splitk=True)
-                self.engine.conv(L, l2, h2, B2, 1, 1, o, False, stream)
+                linear_chain(self.engine, L, [(l0, True, True), (l1, True, True), (l2, False, False)], state, B2, stream, buf,
+                             ("cc_h1", "cc_h2"), out=o, in_ps=ld)
                 n = 2 if key == "center" else 8
                 extra[key + ".r"] = o[:bz, :n].contiguous()
                 extra[key + ".l"] = o[bz:, :n].contiguous()
@@ -613,21 +594,8 @@ class HandsLight(EngineSwitches, nn.Module):
             if extra is not None:
                 output.merge(extra)
             return output
-        Fg = F if self.use_glb_feat_w_grasp else 0
-        gld = P["g0"].Cin
-        gin = buf("grasp_in", B2 * gld)
-        check(L.hands_grasp_input_f32(ptr(state, vo + 96), ld, ptr(rotmat), ptr(feat_vec), ptr(gin), B2, bz,
-                                      Fg, gld, stream), "grasp_input")
-        g1, g2, g3 = buf("g1", B2 * 1024), buf("g2", B2 * 512), buf("g3", B2 * 128)
-        g4 = torch.empty(B2, 12, device=dev)
-        self.engine.conv(L, P["g0"], gin, B2, 1, 1, g1, True, stream, splitk=True)
-        self.engine.conv(L, P["g2"], g1, B2, 1, 1, g2, True, stream, splitk=True)
-        self.engine.conv(L, P["g4"], g2, B2, 1, 1, g3, True, stream, splitk=True)
-        self.engine.conv(L, P["g6"], g3, B2, 1, 1, g4, False, stream)
-        grasp = xdict()
-        grasp["grasp.r"] = g4[:bz, :9].contiguous()
-        grasp["grasp.l"] = g4[bz:, :9].contiguous()
-        output.merge(grasp)
+        output.merge(run_grasp_head(self.engine, L, P["grasp"], GRASP_SPLITK["hands_light"], state, rotmat, bz, stream, buf, shape_ld=ld,
+                                    shape_off=vo + 96, feat=feat_vec, feat_dim=F if self.use_glb_feat_w_grasp else 0))
         if extra is not None:          # model.py:426-433: merged after the grasp outputs
             output.merge(extra)
         return output

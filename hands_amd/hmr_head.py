@@ -1,5 +1,6 @@
 """The heads of hands_light that read the 7x7 feature map: ``HandHMR`` (src/nets/hand_heads/hand_hmr.py:9-92,
-src/nets/hmr_layer.py:7-86) -- parameter containers, packing and the transformer head (tf_decoder=True) -- and the depth head
+src/nets/hmr_layer.py:7-86) -- parameter containers, packing, the iterative head ``iter_head`` and the transformer head ``tf_head``
+(tf_decoder=True), both per hand on one stream -- and the depth head
 (src/models/hands_light/model.py:133-155, 177-185).  The runners take the model's ``engine`` and its workspace allocator
 ``buf(name, numel)``.
 """
@@ -9,7 +10,8 @@ import torch
 import torch.nn as nn
 
 from ._lib import check, ptr
-from .packing import HMR_VEC, hmr_decoder_rows, hmr_state_columns, pack_linear
+from .engine import linear_chain
+from .packing import HMR_VEC, hmr_state_columns, pack_hmr_decoders, pack_linear
 
 
 # parameter containers (names = the reference's state_dict keys; never called)
@@ -131,10 +133,7 @@ def pack_hmr_head(head: HandHMR, dev, feat_dim, tf_decoder):
         P["r0"] = pack_linear(cpu(rf[0].weight), cpu(rf[0].bias), dev, col_index=hmr_state_columns(F),
                               k_total=F + HMR_VEC)
         P["r3"] = pack_linear(cpu(rf[3].weight), cpu(rf[3].bias), dev)
-    d = hl.decoders
-    wd = torch.cat([cpu(d["pose_6d"].weight), cpu(d["shape"].weight), cpu(d["cam_t/wp"].weight)], 0)
-    bd = torch.cat([cpu(d["pose_6d"].bias), cpu(d["shape"].bias), cpu(d["cam_t/wp"].bias)], 0)
-    P["dec"] = pack_linear(wd, bd, dev, row_index=hmr_decoder_rows(), n_total=HMR_VEC)
+    P["dec"] = pack_hmr_decoders(*[(hl.decoders[k].weight, hl.decoders[k].bias) for k in ("pose_6d", "shape", "cam_t/wp")], dev)
     return P
 
 
@@ -165,6 +164,28 @@ def depth_head(engine, buf, L, P, dev, stream, cat, B2, bz, fh, fw, Cr, lda, ldd
     return out[:bz], out[bz:]
 
 
+def cam_init(engine, buf, names, L, hp, stream, x, rows, caminit4, out_off, in_ps=None, x_off=0):
+    """The ``cam_init`` MLP (hand_hmr.py:34-40, 512 -> 512 -> 3 stored 4 wide) on ``rows`` feature rows of ``x`` -> rows of
+    ``caminit4`` from float ``out_off``; ``names``: the two hidden buffers."""
+    linear_chain(engine, L, [(hp["ci0"], True, True), (hp["ci2"], True, True), (hp["ci4"], False, False)], x, rows, stream, buf, names,
+                 out=caminit4, in_ps=in_ps, x_off=x_off, out_off=out_off)
+
+
+def iter_head(engine, buf, L, hp, stream, side, bz, state, caminit4, feat_dim):
+    """``HandHMR.forward`` with tf_decoder=False (hand_hmr.py:73-92, hmr_layer.py:67-86) for one hand: its ``state`` rows
+    [side bz, (side + 1) bz) hold [feat F | vectors 112] with the feat segment filled in -> cam_init, hands_hmr_init_f32, then
+    3 x [refine MLP -> decoders GEMM + residual on the vector columns]; its ``caminit4`` rows."""
+    F, ld = feat_dim, feat_dim + HMR_VEC
+    so, co = side * bz * ld, side * bz * 4
+    cam_init(engine, buf, (f"h512a{side}", f"h512b{side}"), L, hp, stream, state, bz, caminit4, co, in_ps=ld, x_off=so)
+    check(L.hands_hmr_init_f32(ptr(state, so), ptr(caminit4, co), bz, ld, F, stream), "hmr_init")
+    for _ in range(3):
+        x2 = linear_chain(engine, L, [(hp["r0"], True, True), (hp["r3"], True, True)], state, bz, stream, buf,
+                          (f"x1024a{side}", f"x1024b{side}"), in_ps=ld, x_off=so)
+        engine.conv(L, hp["dec"], x2, bz, 1, 1, state, False, stream, res=state, out_ps=ld, res_ps=ld, out_off=so + F, res_off=so + F,
+                    splitk=True)
+
+
 def tf_head(engine, buf, L, hp, stream, side, bz, HW, cat, state, caminit4, feat_dim, Cc, tf_pass=TF_PASS):
     """``HandHMR.forward(features, use_pool=False)`` with tf_decoder=True (hand_hmr.py:57-62, 73-92; hmr_layer.py:67-86) for one
     hand: rows [side bz, (side + 1) bz) of the concatenated map ``cat`` (B2, HW, Cc) -> the vector columns of its ``state``
@@ -185,7 +206,6 @@ def tf_head(engine, buf, L, hp, stream, side, bz, HW, cat, state, caminit4, feat
     cap = min(bz, tf_pass)
     tbuf = lambda nm, numel: buf(f"tf_{nm}{side}", numel)
     mem, kv, pre, pooled = tbuf("mem", cap * HW * E), tbuf("kv", cap * HW * 2 * E), tbuf("pre", cap * HW * F), tbuf("pool", cap * F)
-    h512a, h512b = tbuf("h512a", cap * 512), tbuf("h512b", cap * 512)
     x, att, q, hid = tbuf("x", cap * T * E), tbuf("att", cap * T * E), tbuf("q", cap * T * E), tbuf("hid", cap * T * E)
     qkv, xc = tbuf("qkv", cap * T * 3 * E), tbuf("xc", cap * E)
     scale = float(E) ** -0.5
@@ -204,9 +224,7 @@ def tf_head(engine, buf, L, hp, stream, side, bz, HW, cat, state, caminit4, feat
         # -- init_vector_dict (hand_hmr.py:46-71): cam_init_precursor per pixel BEFORE the average pool
         conv(L, tf["pre"], cat, n * HW, 1, 1, pre, True, stream, x_off=r0 * HW * Cc)
         check(L.hands_avgpool_nhwc_f32(ptr(pre), ptr(pooled), n, HW, F, F, stream), "avgpool")
-        conv(L, hp["ci0"], pooled, n, 1, 1, h512a, True, stream, splitk=True)
-        conv(L, hp["ci2"], h512a, n, 1, 1, h512b, True, stream, splitk=True)
-        conv(L, hp["ci4"], h512b, n, 1, 1, caminit4, False, stream, out_off=co)
+        cam_init(engine, tbuf, ("h512a", "h512b"), L, hp, stream, pooled, n, caminit4, co)
         check(L.hands_hmr_init_f32(ptr(state, so), ptr(caminit4, co), n, HMR_VEC, 0, stream), "hmr_init")
         # -- memory and the cross-attention keys | values
         conv(L, tf["feat_mlp"], cat, n * HW, 1, 1, mem, True, stream, x_off=r0 * HW * Cc)

@@ -154,3 +154,14 @@ def run_mano_heads(L, mano_r, mano_l, rot, shape, cam, cam_init, K, img_res, bz,
 
 
 run_mano_heads.launches_per_step = 1
+
+
+def run_mano_heads_from_pred(L, mano_r, mano_l, pred, K, img_res, bz, stream, buf, engine=None):
+    """The regressor tail of hamer_light / handoccnet_light: ``pred`` (2bz, 112) rows [pose_6d 96 | shape 10 | 2 pad | cam 3 |
+    1 pad] -> rotation matrices (rot6d read by columns, geometry.py:47-62), shape and cam slices -> ``run_mano_heads`` (cam is
+    its own `cam_t.wp.init`).  Returns (output, rot, shape): the grasp head reads the last two."""
+    rot = torch.empty(2 * bz, 16, 3, 3, dtype=torch.float32, device=pred.device)
+    check(L.hands_rot6d_to_matrix_cols_f32(ptr(pred), 112, ptr(rot), 2 * bz, stream), "rot6d_cols")
+    shape = pred[:, 96:106].contiguous()
+    cam = pred[:, 108:111].contiguous()
+    return run_mano_heads(L, mano_r, mano_l, rot, shape, cam, cam, K, img_res, bz, stream, buf, engine), rot, shape

@@ -151,6 +151,13 @@ def hmr_decoder_rows():
     return list(range(96)) + [96 + i for i in range(10)] + [108 + i for i in range(3)]
 
 
+def pack_hmr_decoders(pose, shape, cam, device) -> PackedConv:
+    """The pose_6d (96), shape (10) and cam (3) decoders, each a (weight, bias) pair, stacked as ONE linear layer whose
+    HMR_VEC output columns are the vector part of the state row."""
+    w, b = (torch.cat([p[i].detach().cpu() for p in (pose, shape, cam)], 0) for i in (0, 1))
+    return pack_linear(w, b, device, row_index=hmr_decoder_rows(), n_total=HMR_VEC)
+
+
 def pack_mano(asset: ManoAsset, device):
     """MANO constants for the pose / blend-GEMM / skin kernels.  hands_pack_mano_f32."""
     vt, sd, pd, Jr, hm = (_f32(a) for a in (asset.v_template, asset.shapedirs, asset.posedirs, asset.J_regressor,

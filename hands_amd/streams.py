@@ -29,3 +29,20 @@ class SideJobs:
     def join(self):
         for ev in self.done:
             self.main.wait_event(ev)
+
+
+def run_crop_chunks(main, nch, n, side_stream, job):
+    """Rows [0, n) cut into ``nch`` (1 <= nch <= n) jobs ``job(lo, hi, st, ci)`` that run side by side: the last (largest) chunk on
+    ``main``, chunk ci of the others on ``side_stream(ci)``, each under ``torch.cuda.stream(st)``, forked and joined through
+    :class:`SideJobs`.  One chunk runs on ``main`` as it is: no events, no stream switch.  Returns the jobs' results in order."""
+    if nch == 1:
+        return [job(0, n, main, 0)]
+    jobs, parts = SideJobs(main), []
+    for ci in range(nch):
+        st = main if ci == nch - 1 else side_stream(ci)
+        jobs.begin(st)
+        with torch.cuda.stream(st):
+            parts.append(job(ci * n // nch, (ci + 1) * n // nch, st, ci))
+        jobs.end(st)
+    jobs.join()
+    return parts

@@ -224,3 +224,21 @@ def test_no_kpe_no_grasp_switches_vs_reference_fixture(golden_dir, name):
         verr = np.abs(out[f"mano.vertices.{hn}"].cpu().numpy() - d[f"out/mano.vertices.{hn}"]).max()
         mp = O.mpjpe_ra_mm(out[f"mano.joints3d.{hn}"].cpu(), torch.from_numpy(d[f"out/mano.joints3d.{hn}"]))
         assert verr < 1e-6 and mp < 1e-3, (name, hn, verr, mp)
+
+
+@pytest.mark.parametrize("bz", [2, 1])
+def test_hamer_crop_chunks_are_bit_identical(hamer_gpu, bz):
+    """``HAMER.chunks`` is a launch schedule (streams.run_crop_chunks): three jobs at bz = 2 (4 crops cut 1 / 1 / 2) and the
+    request for three at bz = 1 (2 crops: clamped to two jobs) return every key bit for bit as the single job does."""
+    inputs, meta_info = synthetic_inputs(bz, 5, device=DEV)
+    keep = hamer_gpu.chunks
+    try:
+        outs = {}
+        for n in (1, 3):
+            hamer_gpu.chunks = n
+            outs[n] = {k: v.clone() for k, v in hamer_gpu(inputs, meta_info).items()}
+    finally:
+        hamer_gpu.chunks = keep
+    assert list(outs[3].keys()) == list(outs[1].keys()) and len(outs[1]) == 22
+    for k in outs[1]:
+        assert torch.equal(outs[3][k], outs[1][k]), k

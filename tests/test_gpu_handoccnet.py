@@ -427,3 +427,21 @@ def test_handoccnet_forward_is_bit_identical_without_grouped_launches(hon_gpu):
             hon_gpu.engine.group_launches = True
         for k in a:
             assert torch.equal(a[k], b[k]), (bz, k)
+
+
+def test_handoccnet_crop_chunks_are_bit_identical(hon_gpu):
+    """A forward that runs alone (``async_forward`` off) cuts its crops into ``chunks`` jobs from 128 crops on
+    (streams.run_crop_chunks): bz = 64 as three uneven jobs of 42 / 43 / 43 crops returns every key bit for bit as one job."""
+    inputs, meta_info = synthetic_inputs(64, 6, device=DEV)
+    keep = hon_gpu.chunks
+    hon_gpu.async_forward = False
+    try:
+        outs = {}
+        for n in (1, 3):
+            hon_gpu.chunks = n
+            outs[n] = {k: v.clone() for k, v in hon_gpu(inputs, meta_info).items()}
+    finally:
+        hon_gpu.async_forward, hon_gpu.chunks = True, keep
+    assert list(outs[3].keys()) == list(outs[1].keys()) and len(outs[1]) == 22
+    for k in outs[1]:
+        assert torch.equal(outs[3][k], outs[1][k]), k

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""HandOccNet: the call-site split-K rules for small maps (handoccnet.py _conv_fns) on / off, alternating on ONE model instance
+"""HandOccNet: the call-site split-K rules for small maps (handoccnet.py _conv_fn) on / off, alternating on ONE model instance
 (the rules are read at every forward): hands/s pipelined at 32 and 256 samples, and the latency of one synchronous forward at 2.
 usage (GPU box): python tools/ab_small_map_splitk.py [rounds]"""
 import os
