@@ -74,6 +74,15 @@ class MeshEvalOut(C.Structure):
     _fields_ = [(f"{q}_{s}", C.c_void_p) for q in MESH_QUANTITIES for s in "rlh"]
 
 
+SURF_MAX_F, SURF_CHUNK, SURF_NQ = 4096, 512, 4     # HANDS_SURF_MAX_F, HANDS_SURF_CHUNK, HANDS_SURF_NQ
+SURF_QUANTITIES = ("p2s_ra", "p2s_pa", "chamfer_ra", "chamfer_pa")
+
+
+class SurfEvalOut(C.Structure):
+    """hands_surf_eval_out (include/hands_hip.h): quantity q of hand s (r, l, h) is pointer 3 * q + s."""
+    _fields_ = [(f"{q}_{s}", C.c_void_p) for q in SURF_QUANTITIES for s in "rlh"]
+
+
 class LossIn(C.Structure):
     """hands_loss_in (include/hands_hip.h): the first LOSS_N_MANDATORY pointers are mandatory, the rest come in groups."""
     _fields_ = [(n, C.c_void_p) for n in (
@@ -182,6 +191,8 @@ SIGNATURES = {
     "hands_eval_metrics_f32": [C.POINTER(EvalIn), C.POINTER(EvalOut), _I, _P],
     "hands_eval_metrics_masked_f32": [C.POINTER(EvalIn), _P, _P, C.POINTER(EvalMaskedOut), _I, _P],
     "hands_eval_mesh_metrics_f32": [C.POINTER(MeshEvalIn), C.POINTER(MeshEvalOut), _I, _I, _P],
+    "hands_mesh_closest_f32": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "hands_eval_surface_metrics_f32": [C.POINTER(MeshEvalIn), _P, _P, _I, _I, C.POINTER(SurfEvalOut), _I, _I, _P],
     "hands_loss_light_f32": [C.POINTER(LossIn), _I, _I, _I, _P, _P, _P, _P, _P],
     "hands_mano_pose_aa_f32": [C.POINTER(ManoConsts), _P, _P, _I, _P, _I, _P, _P, _I, _P],
     "hands_gt_targets_f32": [_P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _P],

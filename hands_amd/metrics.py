@@ -9,21 +9,27 @@ takes the other branch of ``eval_mpjpe_pa_ra`` (:231-317, joints flagged in ``jo
 
 ``evaluate_mesh_metrics(pred, targets)`` adds what mesh papers report and the reference does not compute: MPVPE, F@5mm /
 F@15mm and the AUC of the PCK curve, root-aligned and Procrustes-aligned, for the 778 vertices of each hand.
+
+``evaluate_surface_metrics(pred, targets, faces=...)`` measures to the triangle surface instead of the vertices: the
+point-to-surface error scan-based benchmarks report, and the Chamfer distance, under the same two alignments.
 """
 from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
-from ._lib import EvalIn, EvalMaskedOut, EvalOut, MeshEvalIn, MeshEvalOut, check, ptr
+from ._lib import EvalIn, EvalMaskedOut, EvalOut, MeshEvalIn, MeshEvalOut, SurfEvalOut, check, ptr
 from .xdict import xdict
 
 # keys of evaluate_mesh_metrics without the hand suffix, in the order of hands_mesh_eval_out (_lib.MESH_QUANTITIES)
 MESH_KEYS = tuple(k.format(a) for a in ("ra", "pa")
                   for k in ("mpvpe/{}", "fscore/{}/5", "fscore/{}/15", "auc/{}/v", "auc/{}/j"))
 MASKED_KEYS = ("mpjpe/pa/rao", "mpjpe/pa/abs", "mpjpe/pa/ra")
+# keys of evaluate_surface_metrics without the hand suffix, in the order of hands_surf_eval_out (_lib.SURF_QUANTITIES)
+SURF_KEYS = tuple(f"{q}/{a}" for q in ("p2s", "chamfer") for a in ("ra", "pa"))
 
 
 def _is_egoexo(meta_info) -> bool:
@@ -92,3 +98,43 @@ def evaluate_mesh_metrics(pred: dict, targets: dict, meta_info: dict | None = No
     check(L.hands_eval_mesh_metrics_f32(C.byref(MeshEvalIn(*[ptr(t) for t in keep])), C.byref(mout), B, V,
                                         torch.cuda.current_stream(dev).cuda_stream), "hands_eval_mesh_metrics_f32")
     return xdict({f"{k}/{s}": buf[3 * i + j] for i, k in enumerate(MESH_KEYS) for j, s in enumerate("rlh")})
+
+
+def faces_on_device(faces, dev) -> torch.Tensor:
+    """A face list (tensor or numpy array of any integer type, (F,3)) as a contiguous int32 tensor on ``dev``."""
+    t = faces if isinstance(faces, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(faces))
+    if t.is_floating_point() or t.dtype == torch.bool or t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"hands_amd: a face list is an (F, 3) integer array, got {tuple(t.shape)} {t.dtype}")
+    return t.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def evaluate_surface_metrics(pred: dict, targets: dict, meta_info: dict | None = None, faces=None) -> xdict:
+    """Point-to-surface error and Chamfer distance of both hands (hands_eval_surface_metrics_f32, two launches):
+    ``p2s/{ra,pa}/*`` and ``chamfer/{ra,pa}/*`` for ``* = r, l, h``, millimetres, each a (B) tensor on the device of the inputs.
+    With X the aligned prediction, Y the ground truth and T the faces of the hand,
+    ``p2s = 1000 * 1/2 [mean_i d(X_i, surface(Y,T)) + mean_j d(Y_j, surface(X,T))]`` and
+    ``chamfer = 1000 * 1/2 [mean_i min_j |X_i - Y_j| + mean_j min_i |Y_j - X_i|]``; alignments, inputs and NaN rules are those of
+    :func:`evaluate_mesh_metrics`.  The face lists come from ``faces=(faces_r, faces_l)`` or from
+    ``meta_info["mano.faces.{r,l}"]``."""
+    dev = pred["mano.v3d.cam.r"].device
+    if dev.type != "cuda":
+        raise RuntimeError("hands_amd.evaluate_surface_metrics runs on a HIP device only (no CPU fallback)")
+    if faces is None:
+        if meta_info is None or "mano.faces.r" not in meta_info or "mano.faces.l" not in meta_info:
+            raise ValueError("hands_amd.evaluate_surface_metrics needs faces=(faces_r, faces_l) or meta_info['mano.faces.{r,l}']")
+        faces = (meta_info["mano.faces.r"], meta_info["mano.faces.l"])
+    L = _lib.lib()
+    f = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()
+    B, V = pred["mano.v3d.cam.r"].shape[:2]
+    keep = [f(pred["mano.v3d.cam.r"]), f(pred["mano.v3d.cam.l"]), f(targets["mano.v3d.cam.r"]), f(targets["mano.v3d.cam.l"]),
+            f(pred["mano.j3d.cam.r"]), f(pred["mano.j3d.cam.l"]), f(targets["mano.j3d.cam.r"]), f(targets["mano.j3d.cam.l"]),
+            f(targets["is_valid"]), f(targets["right_valid"]), f(targets["left_valid"])]
+    assert all(t.shape == (B, V, 3) for t in keep[:4]) and all(t.shape == (B, 21, 3) for t in keep[4:8])
+    assert all(t.shape == (B,) for t in keep[8:])
+    fr, fl = (faces_on_device(x, dev) for x in faces)
+    buf = torch.empty(len(SURF_KEYS) * 3, B, device=dev)
+    sout = SurfEvalOut(*[ptr(buf[i]) for i in range(buf.shape[0])])
+    check(L.hands_eval_surface_metrics_f32(C.byref(MeshEvalIn(*[ptr(t) for t in keep])), ptr(fr) or None, ptr(fl) or None,
+                                           fr.shape[0], fl.shape[0], C.byref(sout), B, V,
+                                           torch.cuda.current_stream(dev).cuda_stream), "hands_eval_surface_metrics_f32")
+    return xdict({f"{k}/{s}": buf[3 * i + j] for i, k in enumerate(SURF_KEYS) for j, s in enumerate("rlh")})

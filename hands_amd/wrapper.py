@@ -36,7 +36,8 @@ class HandsWrapper(nn.Module):
         self.mano_r = self.model.mano_r.mano
         self.mano_l = self.model.mano_l.mano
         # generic/wrapper.py:44-54.  The four reference names are always evaluated (one launch gives them all); the extra
-        # name "mesh" adds evaluate_mesh_metrics' MPVPE / F-score / AUC keys to what forward(..., "test") returns
+        # name "mesh" adds evaluate_mesh_metrics' MPVPE / F-score / AUC keys to what forward(..., "test") returns, the extra
+        # name "surface" evaluate_surface_metrics' point-to-surface and Chamfer keys
         self.metric_dict = ["mrrpe.rl", "mpjpe.ra", "mpjpe.pa.ra", "pix_err"]
 
     def inference_pose(self, inputs, meta_info):
@@ -141,10 +142,13 @@ class HandsWrapper(nn.Module):
                                 **meta_info.prefix("meta_info.")}).detach()
         if mode == "vis":
             return merged()
-        from .metrics import evaluate_mesh_metrics, evaluate_metrics
+        from .metrics import evaluate_mesh_metrics, evaluate_metrics, evaluate_surface_metrics
         metrics_all = evaluate_metrics(pred, targets, meta_info).detach()
         if "mesh" in self.metric_dict:
             metrics_all.merge(evaluate_mesh_metrics(pred, targets, meta_info).detach())
+        if "surface" in self.metric_dict:
+            faces = (self.model.mano_r.faces, self.model.mano_l.faces)
+            metrics_all.merge(evaluate_surface_metrics(pred, targets, meta_info, faces=faces).detach())
         out_dict = xdict()
         out_dict["imgname"] = meta_info.get("imgname")
         out_dict.merge({"metric." + k: v for k, v in metrics_all.items()})

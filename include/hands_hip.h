@@ -678,6 +678,52 @@ int hands_eval_mesh_metrics_f32(const hands_mesh_eval_in* in, const hands_mesh_e
                                 hands_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Distances from points to a triangle surface (csrc/mesh_distance.hip): brute force over the faces, no acceleration structure,
+ * no allocation, no host synchronisation, no atomics, no runtime call in front of a launch (the launches record into a
+ * hipGraph); bit-reproducible from run to run and independent of the batch a sample sits in.  The reference's lineage measures
+ * the field between two hands to the nearest VERTEX (pytorch3d.ops.knn_points, src/utils/interfield.py); these entries measure
+ * to the surface, and nothing here is pinned to pytorch3d, which is absent.
+ *
+ * hands_mesh_closest_f32: points (B,P,3), verts (B,V,3) fp32, faces (F,3) int32 shared by the batch, valid (B) or NULL.
+ *   dist[b,p]      Euclidean distance from the point to the closed triangle, minimised over the faces: squared distances and
+ *                  their comparison in fp32, a strict < in ascending face order (the lowest index wins an exact tie), one
+ *                  square root at the end.  Point to triangle: the minimum of the three clamped segment distances and, where
+ *                  the normal is not zero and the projection falls inside, the distance to the plane;
+ *   face_idx[b,p]  (or NULL) that face;  closest[b,p] (or NULL) the closest point on it.
+ *   A degenerate face -- a repeated vertex index, collinear vertices -- is the segment or the point it collapses to.  A face with
+ *   an index outside [0, V) or with a non-finite vertex is skipped.  No face left, or F == 0: dist +inf, face_idx -1, closest
+ *   NaN.  A query with a non-finite coordinate: dist NaN, face_idx -1, closest NaN.  A sample with valid[b] == 0: the same, and
+ *   neither its points nor its vertices are read.
+ *   One workgroup per (sample, HANDS_SURF_CHUNK queries); vertices and faces (16-bit indices) in 36 KB of static LDS.
+ *   HANDS_EINVAL (nothing launched): NULL points / verts / dist, NULL faces with F != 0, B, P or V <= 0, F < 0,
+ *   V > HANDS_MESH_MAX_V, F > HANDS_SURF_MAX_F.
+ *
+ * hands_eval_surface_metrics_f32: the inputs and the two alignments (ra, pa) of hands_eval_mesh_metrics_f32, plus the face
+ * list of each hand (F_r, F_l in [0, HANDS_SURF_MAX_F]; NULL only with F == 0).  With X the aligned prediction, Y the ground
+ * truth and T the hand's faces, per hand and alignment, (B) each, millimetres, distances not squared:
+ *   p2s      1000 * 1/2 [ mean_i d(X_i, surface(Y,T)) + mean_j d(Y_j, surface(X,T)) ], d as dist above;
+ *   chamfer  1000 * 1/2 [ mean_i min_j |X_i - Y_j| + mean_j min_i |Y_j - X_i| ], the distances the F-score thresholds.
+ * HANDS_SURF_NQ quantities x {r, l, h}, h = nanmean of r and l.  Sums are fp64 through one fixed tree.  NaN as the mesh
+ * metrics: an invalid hand (not read), a valid hand with any non-finite vertex or joint coordinate, the pa outputs of a constant
+ * prediction; a hand none of whose faces is usable (F == 0, every face with an index outside [0, V)) gives NaN in p2s and
+ * leaves chamfer as it is.  Two launches: one workgroup per (sample, hand, alignment), then h.
+ * HANDS_EINVAL (nothing launched): a NULL pointer, B <= 0, V outside [1, HANDS_MESH_MAX_V], F outside [0, HANDS_SURF_MAX_F].
+ * --------------------------------------------------------------------------------------------- */
+#define HANDS_SURF_MAX_F 4096
+#define HANDS_SURF_CHUNK 512 /* queries per workgroup of hands_mesh_closest_f32 */
+#define HANDS_SURF_NQ 4
+int hands_mesh_closest_f32(const float* points, const float* verts, const int32_t* faces, const float* valid, float* dist,
+                           int32_t* face_idx, float* closest, int B, int P, int V, int F, hands_stream_t stream);
+
+typedef struct hands_surf_eval_out { /* (B) each; quantity q, hand s (r, l, h) is pointer 3 * q + s of the struct */
+  float *p2s_ra_r, *p2s_ra_l, *p2s_ra_h, *p2s_pa_r, *p2s_pa_l, *p2s_pa_h;
+  float *chamfer_ra_r, *chamfer_ra_l, *chamfer_ra_h, *chamfer_pa_r, *chamfer_pa_l, *chamfer_pa_h;
+} hands_surf_eval_out;
+
+int hands_eval_surface_metrics_f32(const hands_mesh_eval_in* in, const int32_t* faces_r, const int32_t* faces_l, int F_r,
+                                   int F_l, const hands_surf_eval_out* out, int B, int V, hands_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The validation loss dict on device, forward only (csrc/loss.hip): compute_loss_light of
  * src/callbacks/loss/loss_arctic_sf.py:20-206 (vector_loss / joints_loss / grasp_loss / render_loss of
  * src/utils/loss_modules.py:97-152) with the weighting and the total of src/models/generic/wrapper.py:19-23,100-115.
