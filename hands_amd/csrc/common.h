@@ -20,6 +20,26 @@ __device__ __forceinline__ float f4e(const float4& v, int t) {
   return t == 0 ? v.x : (t == 1 ? v.y : (t == 2 ? v.z : v.w));
 }
 
+// NaN handling of ReLU and max-pool, one copy for every kernel (torch.relu and nn.MaxPool2d hand a NaN on; fmaxf is IEEE maxNum
+// and drops a NaN operand: fmaxf(NaN, 0) = 0, and a window of NaN alone keeps the -inf its maximum starts from).
+// relu_f32: the bits of fmaxf(v, 0.f) for every v that is not NaN (-0 -> +0), NaN for NaN.
+__device__ __forceinline__ float relu_f32(float v) { return v <= 0.f ? 0.f : v; }
+__device__ __forceinline__ float4 relu_f32(const float4& v) {
+  return make_float4(relu_f32(v.x), relu_f32(v.y), relu_f32(v.z), relu_f32(v.w));
+}
+// One tap of a 4-channel max-pool and its end: the maximum is fmaxf's (finite and infinite windows keep its bits), a flag per
+// channel remembers a NaN tap (one compare per value, the OR on the scalar unit) and replaces the maximum at the end.  Shared by
+// maxpool3x3s2_kernel and the two fused stems, which promise the same bits.
+struct PoolNan4 { bool x = false, y = false, z = false, w = false; };
+__device__ __forceinline__ void pool_tap(float4& m, PoolNan4& seen, const float4& v) {
+  m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+  seen.x |= v.x != v.x; seen.y |= v.y != v.y; seen.z |= v.z != v.z; seen.w |= v.w != v.w;
+}
+__device__ __forceinline__ float4 pool_finish(const float4& m, const PoolNan4& seen) {
+  const float q = __builtin_nanf("");
+  return make_float4(seen.x ? q : m.x, seen.y ? q : m.y, seen.z ? q : m.z, seen.w ? q : m.w);
+}
+
 // exp(x) for finite x <= 0: exp2 of a compensated x * log2(e) (v_exp_f32 on [-0.5, 0.5] + v_ldexp_f32, ~1 ulp; the
 // library's expf carries range checks that cannot trigger here)
 __device__ __forceinline__ float exp_nonpos(float x) {

@@ -31,7 +31,7 @@ __device__ __forceinline__ float gelu_erf(float x) { return x * 0.5f * (1.0f + e
 
 __device__ __forceinline__ float4 apply_act(float4 v, int act) {
   if (act == HANDS_ACT_RELU) {
-    v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+    v = relu_f32(v);                                       // (common.h: NaN stays NaN)
   } else if (act == HANDS_ACT_GELU) {
     v.x = gelu_erf(v.x); v.y = gelu_erf(v.y); v.z = gelu_erf(v.z); v.w = gelu_erf(v.w);
   } else if (act == HANDS_ACT_LEAKY_RELU) {
@@ -215,7 +215,7 @@ __device__ __forceinline__ void splitk_fused_tail(const ConvArgs& a, float* lds,
       for (int sl = 1; sl < a.ksplit; ++sl) v += p[sl * slice];
       float f = (float)(v + (double)a.bias[n]);
       if (a.fin_res) f += a.fin_res[(size_t)m * a.res_ps + n];
-      if (a.fin_act == HANDS_ACT_RELU) f = fmaxf(f, 0.f);
+      if (a.fin_act == HANDS_ACT_RELU) f = relu_f32(f);
       else if (a.fin_act == HANDS_ACT_GELU) f = gelu_erf(f);
       else if (a.fin_act == HANDS_ACT_LEAKY_RELU) f = f > 0.f ? f : 0.01f * f;
       a.out[(size_t)m * a.out_ps + n] = f;
@@ -1018,7 +1018,7 @@ __global__ void splitk_reduce_f64_kernel(const double* __restrict__ partial, int
     for (int s = 1; s < S; ++s) v += partial[((long long)s * M + m) * part_ps + n];
     float f = (float)(v + (double)bias[n]);
     if (res) f += res[m * res_ps + n];
-    if (act == HANDS_ACT_RELU) f = fmaxf(f, 0.f);
+    if (act == HANDS_ACT_RELU) f = relu_f32(f);
     else if (act == HANDS_ACT_GELU) f = gelu_erf(f);
     else if (act == HANDS_ACT_LEAKY_RELU) f = f > 0.f ? f : 0.01f * f;
     out[m * out_ps + n] = f;

@@ -324,8 +324,7 @@ __global__ void __launch_bounds__(256, WINO_WAVES) conv_wino_f32_kernel(WinoArgs
         float4 y0 = add4(add4(add4(z0, z1), z2), bv);
         float4 y1 = add4(sub4(sub4(z1, z2), z3), bv);
         if (a.act == HANDS_ACT_RELU) {
-          y0.x = fmaxf(y0.x, 0.f); y0.y = fmaxf(y0.y, 0.f); y0.z = fmaxf(y0.z, 0.f); y0.w = fmaxf(y0.w, 0.f);
-          y1.x = fmaxf(y1.x, 0.f); y1.y = fmaxf(y1.y, 0.f); y1.z = fmaxf(y1.z, 0.f); y1.w = fmaxf(y1.w, 0.f);
+          y0 = relu_f32(y0); y1 = relu_f32(y1);               // (common.h: NaN stays NaN)
         } else if (a.act == HANDS_ACT_LEAKY_RELU) {
           y0.x = y0.x > 0.f ? y0.x : 0.01f * y0.x; y0.y = y0.y > 0.f ? y0.y : 0.01f * y0.y;
           y0.z = y0.z > 0.f ? y0.z : 0.01f * y0.z; y0.w = y0.w > 0.f ? y0.w : 0.01f * y0.w;

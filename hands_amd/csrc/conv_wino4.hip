@@ -166,7 +166,7 @@ __device__ __forceinline__ void w4_output_pass(const Wino4Args& a, const char* l
   for (int i = 0; i < 4; ++i) {
     float4 v = make_float4(y[i].x + bv.x, y[i].y + bv.y, y[i].z + bv.z, y[i].w + bv.w);
     if (a.act == HANDS_ACT_RELU) {
-      v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+      v = relu_f32(v);                                         // (common.h: NaN stays NaN)
     } else if (a.act == HANDS_ACT_LEAKY_RELU) {
       v.x = v.x > 0.f ? v.x : 0.01f * v.x; v.y = v.y > 0.f ? v.y : 0.01f * v.y;
       v.z = v.z > 0.f ? v.z : 0.01f * v.z; v.w = v.w > 0.f ? v.w : 0.01f * v.w;

@@ -34,6 +34,7 @@ __global__ void maxpool3x3s2_kernel(const float4* __restrict__ in, float4* __res
     const int ho = (int)(t % Ho);
     const int b = (int)(t / Ho);
     float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+    PoolNan4 seen;                                         // (common.h: a NaN tap makes the output NaN, as nn.MaxPool2d does)
 #pragma unroll
     for (int dh = 0; dh < 3; ++dh) {
       const int hi = ho * 2 - 1 + dh;
@@ -43,10 +44,10 @@ __global__ void maxpool3x3s2_kernel(const float4* __restrict__ in, float4* __res
         const int wi = wo * 2 - 1 + dw;
         if ((unsigned)wi >= (unsigned)W) continue;
         const float4 v = in[((long long)(b * H + hi) * W + wi) * C4 + c];
-        m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+        pool_tap(m, seen, v);
       }
     }
-    out[i] = m;
+    out[i] = pool_finish(m, seen);
   }
 }
 

@@ -34,7 +34,7 @@ constexpr int KPAD = 208;                         // 49 taps x 4 channels, padde
 constexpr int ST_ROW = 20;                        // staging row: 16 channels + 4 pad floats (5 slots: odd)
 
 __device__ __forceinline__ float act_scalar(float v, int act) {
-  if (act == HANDS_ACT_RELU) return fmaxf(v, 0.f);
+  if (act == HANDS_ACT_RELU) return relu_f32(v);
   if (act == HANDS_ACT_LEAKY_RELU) return v > 0.f ? v : 0.01f * v;
   return v;
 }
@@ -133,6 +133,7 @@ __global__ void __launch_bounds__(256, 3) stem_pool_kernel(const float4* __restr
       const int gy = PT_H * ty + py, gx = PT_W * tx + px;   // pooled pixel in the image
       if (gy < Hp && gx < Wp) {
         float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+        PoolNan4 seen;
 #pragma unroll
         for (int dy = 0; dy < 3; ++dy) {
           const int ly = 2 * py + dy;                          // row in the convolution tile
@@ -142,9 +143,10 @@ __global__ void __launch_bounds__(256, 3) stem_pool_kernel(const float4* __restr
             const int lx = 2 * px + dx;
             if ((unsigned)(cx0 + lx) >= (unsigned)Wc) continue;
             const float4 v = *reinterpret_cast<const float4*>(stage + (ly * CT_W + lx) * ST_ROW + g * 4);
-            m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+            pool_tap(m, seen, v);
           }
         }
+        m = pool_finish(m, seen);
         const int c = i * 32 + q0 * 8 + g * 4;
         const float4 bv = *reinterpret_cast<const float4*>(bias + c);
         float4 o;
@@ -304,15 +306,15 @@ __global__ void __launch_bounds__(256, 3) stem_pool_planar_kernel(const float* _
     __syncthreads();
     if (pool_ok) {
       float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+      PoolNan4 seen;
 #pragma unroll
       for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
         for (int dx = 0; dx < 3; ++dx) {
           const float4 v = *reinterpret_cast<const float4*>(pst + (dy * CT_W + dx) * ST_ROW);
-          if (tapmask & (1u << (dy * 3 + dx))) {
-            m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
-          }
+          if (tapmask & (1u << (dy * 3 + dx))) pool_tap(m, seen, v);
         }
+      m = pool_finish(m, seen);
       float4 o;
       o.x = act_scalar(m.x + pbias[r].x, act); o.y = act_scalar(m.y + pbias[r].y, act);
       o.z = act_scalar(m.z + pbias[r].z, act); o.w = act_scalar(m.w + pbias[r].w, act);

@@ -95,7 +95,7 @@ typedef struct hands_conv_desc {
 } hands_conv_desc;
 
 #define HANDS_ACT_NONE 0
-#define HANDS_ACT_RELU 1
+#define HANDS_ACT_RELU 1        /* max(x, 0); a NaN stays NaN, as in torch.relu (every convolution entry and the fused stems) */
 #define HANDS_ACT_GELU 2        /* nn.GELU(): x*0.5*(1+erf(x/sqrt(2)))  (vit.py:76, pose_transformer.py:44) */
 #define HANDS_ACT_LEAKY_RELU 3  /* negative slope 0.01 (handoccnet_light/backbone.py) */
 #define HANDS_ACT_MASK 0xff
@@ -267,7 +267,9 @@ int hands_stem_conv_maxpool_nchw_f32(const float* x_nchw, const float* w_planar,
  * Replaces the implicit layout of inputs["img"|"r_img"|"l_img"] (model.py:188,238-239).  B, H, W >= 1, else HANDS_EINVAL. */
 int hands_nchw3_to_nhwc4_f32(const float* in, float* out, int B, int H, int W, hands_stream_t stream);
 
-/* MaxPool2d(kernel 3, stride 2, padding 1) on NHWC.  resnet.py:268. C % 4 == 0; B, H, W >= 1, else HANDS_EINVAL. */
+/* MaxPool2d(kernel 3, stride 2, padding 1) on NHWC.  resnet.py:268. C % 4 == 0; B, H, W >= 1, else HANDS_EINVAL.
+ * A NaN inside a window makes that output NaN, as in nn.MaxPool2d; so does the pool of the two fused stem entries, under
+ * every activation (HANDS_ACT_RELU hands a NaN on as well). */
 int hands_maxpool3x3s2_nhwc_f32(const float* in, float* out, int B, int H, int W, int C,
                                 hands_stream_t stream);
 

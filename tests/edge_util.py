@@ -1,6 +1,7 @@
 """What the edge-shape GPU tests (test_gpu_kernel_edges.py, test_gpu_io_edges.py, test_gpu_conv_edges.py,
-test_gpu_raster_edges.py, test_gpu_mano_edges.py, test_gpu_loss_edges.py) share: guarded output buffers, strided and offset inputs,
-seeded values and the comparisons that print `EDGE|kernel|case|error|bound` before they assert.  A plain module, imported by all six."""
+test_gpu_raster_edges.py, test_gpu_mano_edges.py, test_gpu_loss_edges.py, test_gpu_wino_stem_edges.py) share: guarded output buffers,
+strided and offset inputs, seeded values and the comparisons that print `EDGE|kernel|case|error|bound` before they assert.  A plain
+module, imported by all seven."""
 import math
 
 import torch

@@ -2,7 +2,8 @@
 csrc/metrics.hip and csrc/elementwise.hip, for tests/test_gpu_kernel_edges.py and tests/test_gpu_io_edges.py (csrc/frontend.hip
 has its restatement in oracle/frontend_oracle.py), ``mano_head_ref`` (the MANO head of csrc/mano_lbs.hip with a general K, free
 tip vertices and min_s, for tests/test_gpu_mano_edges.py), and -- last in the file -- ``conv_ref``, the one restatement of the
-convolution entry points of csrc/conv_igemm.hip on flat, strided buffers for tests/test_gpu_conv_edges.py.
+convolution entry points of csrc/conv_igemm.hip on flat, strided buffers for tests/test_gpu_conv_edges.py (and of the same layer
+on the Winograd routes), with ``stem_pool_ref``, the fused stems of csrc/stem_pool.hip, for tests/test_gpu_wino_stem_edges.py.
 
 One function per C entry point of include/hands_hip.h, named after it without ``hands_`` and ``_f32``.  Each takes the entry
 point's arguments in its order -- CPU tensors where the C function takes pointers, with the same layouts (NHWC maps, token rows,
@@ -540,3 +541,34 @@ def conv_ref(d, x, w, bias, res, out, pre=None, dual=None, round_sum=False):
     exp, mag = _d(out).reshape(-1).clone(), _zeros(out.numel())
     exp[idx], mag[idx] = y.reshape(-1), a.reshape(-1)
     return exp.view(out.shape), mag.view(out.shape)
+
+
+# ---- csrc/stem_pool.hip -----------------------------------------------------------------------------------------------------
+class _StemDesc:
+    """The hands_conv_desc of the stem convolution (7x7 / stride 2 / pad 3, 64 channels, no activation) on contiguous pixels."""
+
+    def __init__(self, B, H, W, Cin, Kpad):
+        self.B, self.H, self.W, self.Cin, self.Cout, self.KH, self.KW, self.stride, self.pad = B, H, W, Cin, 64, 7, 7, 2, 3
+        self.Ho, self.Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        self.in_pix_stride, self.out_pix_stride, self.res_pix_stride, self.Kpad, self.act = Cin, 64, 0, Kpad, 0
+
+
+def stem_pool_ref(x, w, bias, B, H, W, act, planar=False):
+    """hands_stem_conv_maxpool_nhwc_f32 (``x`` = the RGB0 image (B, H, W, 4), ``w`` = [>= 64][208], k = (kh, kw, rgb0)) and, with
+    ``planar``, hands_stem_conv_maxpool_nchw_f32 (``x`` = (B, 3, H, W), ``w`` = [>= 64][160], k = plane * 52 + kh * 7 + kw): conv_ref
+    of the 7x7 / 2 / 3 layer on 4 resp. 3 input channels, conv_act, maxpool3x3s2_nhwc, in that order (the kernels add the bias and
+    activate after the maximum: the same value, both being monotone).
+
+    -> (expected, A_pool), both (B, Hp, Wp, 64): A_pool is the window maximum of conv_ref's magnitude A = conv(|x|, |w|) + |bias|,
+    which bounds the pooled error through |max a - max b| <= max |a - b|."""
+    if planar:
+        xs = _d(x).reshape(B, 3, H, W).permute(0, 2, 3, 1).reshape(-1)
+        wp = _d(w).reshape(-1, 160)[:64, :156].reshape(64, 3, 52)[:, :, :49].reshape(64, 3, 7, 7)
+        wk = _zeros(64, 160)
+        wk[:, :147] = wp.permute(0, 2, 3, 1).reshape(64, 147)
+        d = _StemDesc(B, H, W, 3, 160)
+    else:
+        xs, wk, d = _d(x).reshape(-1), _d(w).reshape(-1, 208)[:64], _StemDesc(B, H, W, 4, 208)
+    y, a = conv_ref(d, xs, wk, bias, None, _zeros(B * d.Ho * d.Wo * 64))
+    y = conv_act(y, act)
+    return maxpool3x3s2_nhwc(y, B, d.Ho, d.Wo, 64), maxpool3x3s2_nhwc(a, B, d.Ho, d.Wo, 64)

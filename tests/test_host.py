@@ -236,6 +236,90 @@ def test_bad_descriptors_are_rejected_without_a_gpu():
         _lib.check(10001, "x")
 
 
+def test_the_winograd_edge_tables_reach_what_they_claim():
+    """The case tables of tests/test_gpu_wino_stem_edges.py (pure Python, checked where no GPU is needed): every case leaves its
+    last block partial; the widths, heights, channel pairs and activations of the plan are all there."""
+    import test_gpu_wino_stem_edges as E
+    for kind, t, widths, heights in (("f4", 4, {1, 3, 5, 8, 9, 13, 16, 17, 19, 25, 26, 27, 28, 53, 55, 56, 57}, {1, 3, 4, 5, 9}),
+                                     ("f2", 2, {1, 2, 5, 8, 13, 14, 27, 28, 17, 19, 21, 31}, {1, 2, 3, 7})):
+        cases = E.CASES[kind]
+        assert {c[2] for c in cases} == widths and {c[1] for c in cases} == heights
+        fam = {}
+        for B, H, W, ch, act, gap in cases:
+            per, mul = E._block_rows(kind, W)
+            assert B > 1 and (B * -(-H // t) * mul) % per != 0, (kind, B, H, W)
+            fam.setdefault((per, mul), []).append((ch, act))
+        for key, seen in fam.items():
+            assert {a for _, a in seen} == {0, 1, 3}, (kind, key)
+        for ch in range(len(E.CHANNELS[kind])):
+            assert any(c[3] == ch and E._block_rows(kind, c[2])[0] == 32 for c in cases), (kind, ch, "no linear geometry")
+            assert any(c[3] == ch and E._block_rows(kind, c[2])[0] != 32 for c in cases), (kind, ch, "no rectangular geometry")
+        assert len(cases) / 4 <= sum(c[5] for c in cases) <= len(cases) / 2
+
+
+def _wino_desc(B, H, W, Cin, Cout, in_ps=None, out_ps=None, act=1):
+    return _lib.ConvDesc(B, H, W, Cin, H, W, Cout, 3, 3, 1, 1, in_ps or Cin, out_ps or Cout, 0, 9 * Cin, act)
+
+
+def _wino_entries(L, which):
+    return {"f4": (L.hands_conv3x3_winograd4_supported, L.hands_conv3x3_winograd4_executed_macs),
+            "f2": (L.hands_conv3x3_winograd_supported, L.hands_conv3x3_winograd_executed_macs)}[which]
+
+
+@pytest.mark.parametrize("which,tile,reach", [("f4", 4, 16), ("f2", 2, 8)])
+def test_winograd_32bit_offset_limits_without_a_gpu(which, tile, reach):
+    """w4_ok / wino_sizes_ok: byte offsets count from the first image a block touches and must stay below 2^31 over the
+    (reach / nh + 2) images it can reach, on the wider of the two pixel strides; tile indices stay below 0x7fffff00.  Nothing is
+    launched, so the maps may be as large as the limits."""
+    supported, macs = _wino_entries(_lib.lib(), which)
+    lim = lambda H, W, ps: (reach // -(-H // tile) + 2) * H * W * ps * 4
+    cases = []
+    # nh = 256 resp. 512 tile rows: two images.  2 * 2^20 pixels * ps * 4 bytes = ps * 2^23: 252 floats inside, 256 = 2^31 outside
+    for wide in ("in", "out"):
+        for ps, ok in ((252, 1), (256, 0)):
+            cases.append((_wino_desc(1, 1024, 1024, 224, 224, **{wide + "_ps": ps}), lim(1024, 1024, ps), ok))
+    # nh = 1: reach + 2 images of one tile row.  F(4x4): 18 * 4 * 65536 * ps * 4 -> ps < 113.8; F(2x2): 10 * 2 * 65536 * ps * 4 -> ps < 409.6
+    lo, hi = (112, 116) if which == "f4" else (408, 412)
+    for ps, ok in ((lo, 1), (hi, 0)):
+        cases.append((_wino_desc(1, tile, 65536, 32, 96, out_ps=ps), lim(tile, 65536, ps), ok))
+    for d, bytes_, ok in cases:
+        assert (bytes_ < 2 ** 31) == bool(ok)                                     # the pair really brackets the limit
+        assert supported(ctypes.byref(d)) == ok and (macs(ctypes.byref(d)) > 0) == bool(ok), (d.H, d.W, d.in_pix_stride, d.out_pix_stride)
+    # rows * nw < 0x7fffff00 with nw = 2 (W = tile + 1), one tile row per image: B = rows
+    for B, ok in ((0x7fffff00 // 2 - 1, 1), (0x7fffff00 // 2, 0)):
+        d = _wino_desc(B, 1, tile + 1, 16, 32)
+        assert (B * 2 < 0x7fffff00) == bool(ok)
+        assert supported(ctypes.byref(d)) == ok and (macs(ctypes.byref(d)) > 0) == bool(ok), B
+
+
+def test_winograd_executed_macs_without_a_gpu():
+    """hands_conv3x3_winograd_executed_macs (bench.py reports it): 0 for what the route cannot take, never below the 16
+    multiplications per 2x2 tile and (cin, cout) pair, and exactly that where no tile lane idles."""
+    L = _lib.lib()
+    macs = L.hands_conv3x3_winograd_executed_macs
+    assert macs(None) == 0
+    for field, val in (("stride", 2), ("pad", 0), ("KH", 1), ("Cin", 24), ("Cout", 48), ("act", 2), ("act", 1 | 0x100),
+                       ("in_pix_stride", 66), ("out_pix_stride", 32), ("Ho", 13), ("B", 0), ("H", 0)):
+        d = _lib.ConvDesc(2, 14, 14, 64, 14, 14, 64, 3, 3, 1, 1, 64, 64, 0, 576, 1)
+        setattr(d, field, val)
+        assert L.hands_conv3x3_winograd_supported(ctypes.byref(d)) == 0 and macs(ctypes.byref(d)) == 0, field
+    tiles = lambda B, H, W: B * -(-H // 2) * -(-W // 2)
+    for B, H, W, Cin, Cout in ((3, 56, 56, 64, 64), (5, 28, 28, 128, 128), (7, 14, 14, 256, 256), (9, 7, 7, 512, 512), (2, 1, 1, 16, 32),
+                               (1, 9, 11, 48, 96), (2, 20, 19, 32, 32), (4, 13, 14, 64, 32), (3, 5, 31, 16, 32), (5, 3, 27, 32, 96)):
+        got = macs(ctypes.byref(_wino_desc(B, H, W, Cin, Cout)))
+        assert got >= 16 * tiles(B, H, W) * Cin * Cout and got % (16 * 32 * Cin * Cout) == 0, (B, H, W)
+    # no idle lane: a block is 32 tiles -- 8 tile rows x 4 columns (D = 4), 4 x 8 (D = 8) or 32 consecutive tiles of 7- and 14-wide
+    # maps (conv_wino.hip, WinoGeom::NR and the linear order).  Even maps that fill whole blocks:
+    for B, H, W, full in ((2, 8, 8, True),        # D = 4: nh = nw = 4, the two images' 8 tile rows are ONE 8 x 4 block
+                          (6, 8, 32, True),       # D = 4: 24 tile rows x 16 columns = 3 x 4 blocks
+                          (32, 14, 14, True),     # linear: 224 tile rows of 7 = 49 blocks of 32 consecutive tiles
+                          (8, 4, 28, True),       # linear, two virtual rows: 16 tile rows of 14 = 7 blocks
+                          (1, 8, 32, False),      # D = 4 with 4 tile rows: half of every block idles
+                          (2, 4, 20, False)):     # D = 8 (nw = 10): its second segment holds 2 of 8 columns
+        got, exact = macs(ctypes.byref(_wino_desc(B, H, W, 16, 32))), 16 * tiles(B, H, W) * 16 * 32
+        assert (got == exact) if full else (got > exact), (B, H, W, got, exact)
+
+
 def test_product_refuses_cpu_tensors(recipe_model):
     inputs, meta = hands_amd.synthetic_inputs(1, 0)
     with pytest.raises(RuntimeError, match="no CPU fallback"):

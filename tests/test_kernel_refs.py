@@ -508,6 +508,36 @@ def test_conv_ref_against_aten(B, Cin, H, W, Cout, KH, KW, stride, pad, act):
         assert (_nchw(rs.view(B, d.Ho, d.Wo, Cout)) != s.double()).float().mean().item() < 1e-3      # ties of the fp64 sum's order only
 
 
+# ---- stem_pool_ref: the fused stem entries (tests/test_gpu_wino_stem_edges.py) -------------------------------------------------
+@pytest.mark.parametrize("B,H,W,act,negative", [
+    (1, 25, 29, 1, False), (1, 25, 29, 3, False),          # Hc = 13, Wc = 15: the last pool windows have two taps per axis
+    (2, 7, 7, 0, True), (2, 29, 33, 3, True)])             # every convolution output negative: a 0 as pool padding would win
+def test_stem_pool_ref_against_aten(B, H, W, act, negative):
+    x, w, bias = _rand(400, B, 3, H, W), _rand(401, 64, 3, 7, 7) / 147 ** 0.5, _rand(402, 64)
+    if negative:                       # the construction of test_stem_all_negative: negative with and without the bias
+        x, w, bias = x.abs() + 0.1, -0.25 * w.abs(), torch.full((64,), -8.0, dtype=torch.float64)
+    t = F.conv2d(x, w, bias, 2, 3)
+    assert t.shape[2:] == ((H - 1) // 2 + 1, (W - 1) // 2 + 1) and (not negative or t.max().item() < -8)
+    fn = {0: lambda v: v, 1: F.relu, 3: lambda v: F.leaky_relu(v, 0.01)}[act]
+    ref = F.max_pool2d(fn(t), 3, 2, 1).permute(0, 2, 3, 1)
+    amag = F.max_pool2d(F.conv2d(x.abs(), w.abs(), bias.abs(), 2, 3), 3, 2, 1).permute(0, 2, 3, 1)
+    if negative and act != 1:
+        assert ref.max().item() < 0                                                          # ... and nothing here is one
+    x4 = torch.cat([x.permute(0, 2, 3, 1), torch.zeros(B, H, W, 1, dtype=torch.float64)], -1)
+    w4 = torch.zeros(128, 208, dtype=torch.float64)
+    w4[:64, :196] = torch.cat([w.permute(0, 2, 3, 1), torch.zeros(64, 7, 7, 1, dtype=torch.float64)], -1).reshape(64, 196)
+    wpl = torch.zeros(64, 3, 52, dtype=torch.float64)
+    wpl[:, :, :49] = w.reshape(64, 3, 49)
+    wpl = torch.cat([wpl.reshape(64, 156), torch.zeros(64, 4, dtype=torch.float64)], 1)
+    for got, mag in (R.stem_pool_ref(x4, w4, bias, B, H, W, act), R.stem_pool_ref(x, wpl, bias, B, H, W, act, planar=True)):
+        assert got.shape == ref.shape == mag.shape and got.dtype == torch.float64
+        assert (got - ref).abs().max().item() < F64 and (mag - amag).abs().max().item() < F64
+        assert torch.all(mag >= got.abs() * (1 - 1e-12))
+    with R.precision(torch.float32):
+        g32, _ = R.stem_pool_ref(x4, w4, bias, B, H, W, act)
+    assert g32.dtype == torch.float32 and (g32.double() - ref).abs().max().item() < 1e-4
+
+
 # ---- mano_head_ref ----------------------------------------------------------------------------------------------------------
 def _mano_assets():
     import fake_mano
