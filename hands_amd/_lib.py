@@ -75,6 +75,7 @@ class MeshEvalOut(C.Structure):
 
 
 SURF_MAX_F, SURF_CHUNK, SURF_NQ = 4096, 512, 4     # HANDS_SURF_MAX_F, HANDS_SURF_CHUNK, HANDS_SURF_NQ
+SIGNED_CHUNK = 256                                 # HANDS_SIGNED_CHUNK
 SURF_QUANTITIES = ("p2s_ra", "p2s_pa", "chamfer_ra", "chamfer_pa")
 
 
@@ -192,6 +193,7 @@ SIGNATURES = {
     "hands_eval_metrics_masked_f32": [C.POINTER(EvalIn), _P, _P, C.POINTER(EvalMaskedOut), _I, _P],
     "hands_eval_mesh_metrics_f32": [C.POINTER(MeshEvalIn), C.POINTER(MeshEvalOut), _I, _I, _P],
     "hands_mesh_closest_f32": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "hands_mesh_signed_f32": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "hands_eval_surface_metrics_f32": [C.POINTER(MeshEvalIn), _P, _P, _I, _I, C.POINTER(SurfEvalOut), _I, _I, _P],
     "hands_loss_light_f32": [C.POINTER(LossIn), _I, _I, _I, _P, _P, _P, _P, _P],
     "hands_mano_pose_aa_f32": [C.POINTER(ManoConsts), _P, _P, _I, _P, _I, _P, _P, _I, _P],

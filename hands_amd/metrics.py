@@ -12,6 +12,9 @@ F@15mm and the AUC of the PCK curve, root-aligned and Procrustes-aligned, for th
 
 ``evaluate_surface_metrics(pred, targets, faces=...)`` measures to the triangle surface instead of the vertices: the
 point-to-surface error scan-based benchmarks report, and the Chamfer distance, under the same two alignments.
+
+``evaluate_penetration_metrics(pred, targets, faces=...)`` scores the prediction alone: how deep, with how many vertices and
+-- on request -- with what volume the two predicted hands pass through each other (hands_amd/penetration.py).
 """
 from __future__ import annotations
 
@@ -138,3 +141,40 @@ def evaluate_surface_metrics(pred: dict, targets: dict, meta_info: dict | None =
                                            fr.shape[0], fl.shape[0], C.byref(sout), B, V,
                                            torch.cuda.current_stream(dev).cuda_stream), "hands_eval_surface_metrics_f32")
     return xdict({f"{k}/{s}": buf[3 * i + j] for i, k in enumerate(SURF_KEYS) for j, s in enumerate("rlh")})
+
+
+PEN_KEYS = ("pen/depth", "pen/count")
+
+
+def evaluate_penetration_metrics(pred: dict, targets: dict, meta_info: dict | None = None, faces=None, seal=True,
+                                 volume_grid=0) -> xdict:
+    """How far the two PREDICTED hands pass through each other (hands_mesh_signed_f32, two launches; the ground truth gives
+    the validity flags only): ``pen/depth/*`` the deepest vertex below the other hand's surface in millimetres and
+    ``pen/count/*`` the number of vertices inside it, for ``* = r`` (the right hand's vertices in the left hand), ``l`` and
+    ``h``, the larger of the two; with ``volume_grid = G > 0`` also ``pen/volume/h``, the volume both hands occupy in cubic
+    centimetres on a ``G^3`` grid (:func:`hands_amd.intersection_volume`, two more launches).  Each a (B) fp32 tensor on the
+    device of the inputs; a sample with ``is_valid * right_valid * left_valid == 0`` is NaN, as is one with a non-finite vertex.
+    ``seal`` closes each hand's open boundary first (:func:`hands_amd.seal_mesh`).  The face lists come from
+    ``faces=(faces_r, faces_l)`` or from ``meta_info["mano.faces.{r,l}"]``."""
+    from .penetration import interhand_penetration, intersection_volume
+    dev = pred["mano.v3d.cam.r"].device
+    if dev.type != "cuda":
+        raise RuntimeError("hands_amd.evaluate_penetration_metrics runs on a HIP device only (no CPU fallback)")
+    if faces is None:
+        if meta_info is None or "mano.faces.r" not in meta_info or "mano.faces.l" not in meta_info:
+            raise ValueError("hands_amd.evaluate_penetration_metrics needs faces=(faces_r, faces_l) or meta_info['mano.faces.{r,l}']")
+        faces = (meta_info["mano.faces.r"], meta_info["mano.faces.l"])
+    d = {"mano.v3d.cam.r": pred["mano.v3d.cam.r"], "mano.v3d.cam.l": pred["mano.v3d.cam.l"]}
+    for k in ("is_valid", "right_valid", "left_valid"):
+        d[k] = targets[k].to(dev)
+    pen = interhand_penetration(d, faces=faces, seal=seal)
+    nan = torch.isnan(pen["pen.depth.rl"]) | torch.isnan(pen["pen.depth.lr"])        # not valid, or a non-finite vertex
+    out = xdict()
+    for key, name, scale in (("pen/depth", "pen.depth", 1000.0), ("pen/count", "pen.count", 1.0)):
+        r, l = (torch.where(nan, torch.full_like(nan, float("nan"), dtype=torch.float32), pen[f"{name}.{k}"].float() * scale)
+                for k in ("rl", "lr"))
+        out[key + "/r"], out[key + "/l"], out[key + "/h"] = r, l, torch.maximum(r, l)
+    if volume_grid:
+        vol = intersection_volume(d, faces=faces, seal=seal, G=int(volume_grid)) * 1e6
+        out["pen/volume/h"] = torch.where(nan, torch.full_like(vol, float("nan")), vol)
+    return out

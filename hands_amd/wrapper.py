@@ -37,8 +37,11 @@ class HandsWrapper(nn.Module):
         self.mano_l = self.model.mano_l.mano
         # generic/wrapper.py:44-54.  The four reference names are always evaluated (one launch gives them all); the extra
         # name "mesh" adds evaluate_mesh_metrics' MPVPE / F-score / AUC keys to what forward(..., "test") returns, the extra
-        # name "surface" evaluate_surface_metrics' point-to-surface and Chamfer keys
+        # name "surface" evaluate_surface_metrics' point-to-surface and Chamfer keys, the extra name "penetration"
+        # evaluate_penetration_metrics' depth and count keys (penetration_seal is handed on as its `seal`: a model whose face
+        # lists cannot be sealed, such as the synthetic asset's, sets it to False)
         self.metric_dict = ["mrrpe.rl", "mpjpe.ra", "mpjpe.pa.ra", "pix_err"]
+        self.penetration_seal = True
 
     def inference_pose(self, inputs, meta_info):
         pred = self.model(inputs, meta_info)
@@ -149,6 +152,10 @@ class HandsWrapper(nn.Module):
         if "surface" in self.metric_dict:
             faces = (self.model.mano_r.faces, self.model.mano_l.faces)
             metrics_all.merge(evaluate_surface_metrics(pred, targets, meta_info, faces=faces).detach())
+        if "penetration" in self.metric_dict:
+            from .metrics import evaluate_penetration_metrics
+            faces = (self.model.mano_r.faces, self.model.mano_l.faces)
+            metrics_all.merge(evaluate_penetration_metrics(pred, targets, meta_info, faces=faces, seal=self.penetration_seal).detach())
         out_dict = xdict()
         out_dict["imgname"] = meta_info.get("imgname")
         out_dict.merge({"metric." + k: v for k, v in metrics_all.items()})

@@ -700,6 +700,22 @@ int hands_eval_mesh_metrics_f32(const hands_mesh_eval_in* in, const hands_mesh_e
  *   HANDS_EINVAL (nothing launched): NULL points / verts / dist, NULL faces with F != 0, B, P or V <= 0, F < 0,
  *   V > HANDS_MESH_MAX_V, F > HANDS_SURF_MAX_F.
  *
+ * hands_mesh_signed_f32 (csrc/mesh_signed.hip): the inputs, limits, skip and tie rules of hands_mesh_closest_f32; the same walk over the faces also sums
+ * the generalised winding number of the mesh about the query (Jacobson et al. 2013),
+ *   w(p) = 1/(4 pi) sum_f Omega_f,  Omega_f = 2 atan2( a . (b x c), |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b| ),
+ * a = v0 - p, b = v1 - p, c = v2 - p (Van Oosterom & Strackee 1983), fp32, in ascending face order in one lane.  A term whose two
+ * arguments are both 0 (a query on a vertex of the face) is 0, as is the term of a face whose fp32 normal is exactly zero (a
+ * repeated index: the face hands_mesh_closest_f32 treats as a segment or a point); a skipped face adds nothing.  For a
+ * closed, outward-oriented mesh w is 1 inside and 0 outside, -1 inside where the faces are oriented inwards.
+ *   winding[b,p]   (or NULL) w;
+ *   sdf[b,p]       -dist where |w| >= 0.5, else +dist, dist as hands_mesh_closest_f32 gives it;
+ *   face_idx[b,p]  (or NULL) the closest face.
+ *   No face left, or F == 0: winding 0, sdf +inf, face_idx -1.  A query with a non-finite coordinate, or valid[b] == 0 (nothing
+ *   of the sample is read): winding NaN, sdf NaN, face_idx -1.  The mesh has to be closed for the sign to mean anything: an open
+ *   boundary (MANO's wrist) leaves w near 0.5 around it -- hands_amd.seal_mesh closes it on the host.
+ *   One workgroup per (sample, HANDS_SIGNED_CHUNK queries), a lane owns one query.  HANDS_EINVAL as hands_mesh_closest_f32, with
+ *   sdf in the place of dist.
+ *
  * hands_eval_surface_metrics_f32: the inputs and the two alignments (ra, pa) of hands_eval_mesh_metrics_f32, plus the face
  * list of each hand (F_r, F_l in [0, HANDS_SURF_MAX_F]; NULL only with F == 0).  With X the aligned prediction, Y the ground
  * truth and T the hand's faces, per hand and alignment, (B) each, millimetres, distances not squared:
@@ -716,6 +732,9 @@ int hands_eval_mesh_metrics_f32(const hands_mesh_eval_in* in, const hands_mesh_e
 #define HANDS_SURF_NQ 4
 int hands_mesh_closest_f32(const float* points, const float* verts, const int32_t* faces, const float* valid, float* dist,
                            int32_t* face_idx, float* closest, int B, int P, int V, int F, hands_stream_t stream);
+#define HANDS_SIGNED_CHUNK 256 /* queries per workgroup of hands_mesh_signed_f32 */
+int hands_mesh_signed_f32(const float* points, const float* verts, const int32_t* faces, const float* valid, float* sdf,
+                          float* winding, int32_t* face_idx, int B, int P, int V, int F, hands_stream_t stream);
 
 typedef struct hands_surf_eval_out { /* (B) each; quantity q, hand s (r, l, h) is pointer 3 * q + s of the struct */
   float *p2s_ra_r, *p2s_ra_l, *p2s_ra_h, *p2s_pa_r, *p2s_pa_l, *p2s_pa_h;
