@@ -20,10 +20,12 @@ from .metrics import evaluate_penetration_metrics  # noqa: F401
 from .surface import closest_on_mesh, interhand_field  # noqa: F401
 from .penetration import (seal_mesh, apply_seal, signed_distance_to_mesh, interhand_penetration, penetration_grid,  # noqa: F401
                           intersection_volume)
+from .temporal import accel_error, evaluate_accel_metrics, AccelMetrics  # noqa: F401
 
 __all__ = ["HandsLight", "DEFAULT_ARGS", "ManoHeadsPlan", "HAMER", "HAMER_DEFAULT_ARGS", "HandOccNet", "HANDOCC_DEFAULT_ARGS", "xdict", "prefix_dict", "ManoAsset", "synthetic_mano_asset",
            "build_mano_asset", "apply_recipe", "synthetic_inputs", "HandsFrontEnd", "GraphedForward", "HandsWrapper",
            "HaMeRWrapper", "HandOccNetWrapper", "MANORenderer", "rasterize", "Renderer", "denormalize_images", "sideview_transform",
            "compute_loss_light", "mul_loss_dict", "total_loss", "epoch_end", "evaluate_metrics", "evaluate_mesh_metrics",
            "evaluate_surface_metrics", "closest_on_mesh", "interhand_field", "evaluate_penetration_metrics", "seal_mesh", "apply_seal",
-           "signed_distance_to_mesh", "interhand_penetration", "penetration_grid", "intersection_volume"]
+           "signed_distance_to_mesh", "interhand_penetration", "penetration_grid", "intersection_volume",
+           "accel_error", "evaluate_accel_metrics", "AccelMetrics"]

@@ -84,6 +84,15 @@ class SurfEvalOut(C.Structure):
     _fields_ = [(f"{q}_{s}", C.c_void_p) for q in SURF_QUANTITIES for s in "rlh"]
 
 
+ACCEL_NQ = 3                                       # HANDS_ACCEL_NQ
+ACCEL_QUANTITIES = ("acc", "acc_j", "acc_abs")
+
+
+class AccelEvalOut(C.Structure):
+    """hands_accel_eval_out (include/hands_hip.h): quantity q of hand s (r, l, h) is pointer 3 * q + s."""
+    _fields_ = [(f"{q}_{s}", C.c_void_p) for q in ACCEL_QUANTITIES for s in "rlh"]
+
+
 class LossIn(C.Structure):
     """hands_loss_in (include/hands_hip.h): the first LOSS_N_MANDATORY pointers are mandatory, the rest come in groups."""
     _fields_ = [(n, C.c_void_p) for n in (
@@ -195,6 +204,8 @@ SIGNATURES = {
     "hands_mesh_closest_f32": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "hands_mesh_signed_f32": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "hands_eval_surface_metrics_f32": [C.POINTER(MeshEvalIn), _P, _P, _I, _I, C.POINTER(SurfEvalOut), _I, _I, _P],
+    "hands_accel_error_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _P],
+    "hands_eval_accel_metrics_f32": [C.POINTER(MeshEvalIn), _P, C.POINTER(AccelEvalOut), _I, _I, _F, _P],
     "hands_loss_light_f32": [C.POINTER(LossIn), _I, _I, _I, _P, _P, _P, _P, _P],
     "hands_mano_pose_aa_f32": [C.POINTER(ManoConsts), _P, _P, _I, _P, _I, _P, _P, _I, _P],
     "hands_gt_targets_f32": [_P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _P],

@@ -39,9 +39,12 @@ class HandsWrapper(nn.Module):
         # name "mesh" adds evaluate_mesh_metrics' MPVPE / F-score / AUC keys to what forward(..., "test") returns, the extra
         # name "surface" evaluate_surface_metrics' point-to-surface and Chamfer keys, the extra name "penetration"
         # evaluate_penetration_metrics' depth and count keys (penetration_seal is handed on as its `seal`: a model whose face
-        # lists cannot be sealed, such as the synthetic asset's, sets it to False)
+        # lists cannot be sealed, such as the synthetic asset's, sets it to False), the extra name "accel" the acceleration
+        # errors acc/*, acc/j/*, acc/abs/* of hands_amd.AccelMetrics: consecutive calls are read as consecutive frames at
+        # accel_fps, sequences told apart by meta_info["seq_id"] where it is given; reset_accel() starts a new stream
         self.metric_dict = ["mrrpe.rl", "mpjpe.ra", "mpjpe.pa.ra", "pix_err"]
         self.penetration_seal = True
+        self.accel_fps = 30.0
 
     def inference_pose(self, inputs, meta_info):
         pred = self.model(inputs, meta_info)
@@ -108,6 +111,19 @@ class HandsWrapper(nn.Module):
             self.__dict__["_mask_renderer_obj"] = r
         return r
 
+    def _accel_metrics(self):
+        """The streaming acceleration metrics, built on first use with ``accel_fps``."""
+        a = self.__dict__.get("_accel_metrics_obj")
+        if a is None:
+            from .temporal import AccelMetrics
+            a = AccelMetrics(self.accel_fps)
+            self.__dict__["_accel_metrics_obj"] = a
+        return a
+
+    def reset_accel(self):
+        """Forget the frames the "accel" metrics carry from one ``forward`` to the next (a new stream; ``accel_fps`` is read again)."""
+        self.__dict__.pop("_accel_metrics_obj", None)
+
     def forward(self, inputs, targets=None, meta_info=None, mode="test", compute_loss=False, loss_args=None):
         """GenericWrapper.forward without the training parts (src/models/generic/wrapper.py:77-164):
         GT preprocessing -> model -> [loss dict] -> 2-D de-normalisation -> metrics (``test``) / merged dict
@@ -156,6 +172,8 @@ class HandsWrapper(nn.Module):
             from .metrics import evaluate_penetration_metrics
             faces = (self.model.mano_r.faces, self.model.mano_l.faces)
             metrics_all.merge(evaluate_penetration_metrics(pred, targets, meta_info, faces=faces, seal=self.penetration_seal).detach())
+        if "accel" in self.metric_dict and mode == "test":                 # "extract" returns no metric: it is no frame of the stream
+            metrics_all.merge(self._accel_metrics().update(pred, targets, meta_info).detach())
         out_dict = xdict()
         out_dict["imgname"] = meta_info.get("imgname")
         out_dict.merge({"metric." + k: v for k, v in metrics_all.items()})

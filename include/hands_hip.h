@@ -745,6 +745,44 @@ int hands_eval_surface_metrics_f32(const hands_mesh_eval_in* in, const int32_t* 
                                    int F_l, const hands_surf_eval_out* out, int B, int V, hands_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Temporal metrics on device (csrc/accel.hip): the acceleration error of compute_error_accel / eval_acc_pose
+ * (src/utils/eval_modules.py:508-622) over T consecutive frames given in order, metres per second squared.  One launch per
+ * entry, one workgroup per output row, no allocation, no host synchronisation, no atomics: the bits of a row depend on its
+ * three frames alone -- not on T, on the row's position or on the run.
+ *
+ * hands_accel_error_f32: gt, pred (T,N,D) fp32 with D in 1..3, valid (T) or NULL, seq_id (T) or NULL, fps > 0.
+ *   a[t] = (x[t-1] - 2 x[t] + x[t+1]) fps^2,   out[t] = mean_n | a_pred[t,n,:] - a_gt[t,n,:] |_2   for 1 <= t <= T-2;
+ *   rows 0 and T-1 are NaN, the layout of eval_acc_pose after its padding.  Row t is NaN, and no coordinate of its window is
+ *   read, when one of the frames t-1, t, t+1 has valid == 0 (NULL: every frame is valid) or when the three frames do not carry
+ *   the same seq_id (NULL: the call is one sequence, as in the reference).  Inputs are fp32, everything from the first
+ *   subtraction on is fp64, the result is rounded once to fp32.  A non-finite coordinate in a valid window propagates as IEEE
+ *   arithmetic propagates it (a NaN gives NaN, an infinity +inf or NaN), with no special case.  No upper limit on N: a lane walks
+ *   the points lane, lane + 256, ...  Sums are fp64 in one fixed order: the lane's points in index order, a shuffle tree inside
+ *   the wave, the waves in order.
+ *   HANDS_EINVAL (nothing launched): NULL gt / pred / out, T <= 0, N <= 0, D outside 1..3, fps not finite or <= 0.
+ *
+ * hands_eval_accel_metrics_f32: the inputs of hands_eval_mesh_metrics_f32 with B read as T (any V >= 1), seq_id (T) or NULL.
+ *   A hand's frame is valid where {right,left}_valid * is_valid != 0; the window and sequence rules are those above, per hand.
+ *   HANDS_ACCEL_NQ quantities x {r, l, h}, (T) each, h = nanmean of r and l (NaN when both are):
+ *     acc      the V vertices, root-relative: joint 0 of j3d of the same frame subtracted, pred from pred and gt from gt
+ *              (acc_h is the reference's acc/h);
+ *     acc_j    the 21 joints, root-relative;
+ *     acc_abs  the 21 joints as they are (camera space).
+ *   Both hands of a row in one workgroup.  HANDS_EINVAL (nothing launched): a NULL in, out or member of either, T <= 0,
+ *   V <= 0, fps not finite or <= 0.
+ * --------------------------------------------------------------------------------------------- */
+#define HANDS_ACCEL_NQ 3
+int hands_accel_error_f32(const float* gt, const float* pred, const float* valid, const int32_t* seq_id, float* out, int T,
+                          int N, int D, float fps, hands_stream_t stream);
+
+typedef struct hands_accel_eval_out { /* (T) each; quantity q, hand s (r, l, h) is pointer 3 * q + s of the struct */
+  float *acc_r, *acc_l, *acc_h, *acc_j_r, *acc_j_l, *acc_j_h, *acc_abs_r, *acc_abs_l, *acc_abs_h;
+} hands_accel_eval_out;
+
+int hands_eval_accel_metrics_f32(const hands_mesh_eval_in* in, const int32_t* seq_id, const hands_accel_eval_out* out, int T,
+                                 int V, float fps, hands_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The validation loss dict on device, forward only (csrc/loss.hip): compute_loss_light of
  * src/callbacks/loss/loss_arctic_sf.py:20-206 (vector_loss / joints_loss / grasp_loss / render_loss of
  * src/utils/loss_modules.py:97-152) with the weighting and the total of src/models/generic/wrapper.py:19-23,100-115.
