@@ -93,6 +93,19 @@ class AccelEvalOut(C.Structure):
     _fields_ = [(f"{q}_{s}", C.c_void_p) for q in ACCEL_QUANTITIES for s in "rlh"]
 
 
+class SmoothSide(C.Structure):
+    """hands_smooth_side (include/hands_hip.h): one hand of a hands_smooth_mano_f32 call; valid and state may be NULL."""
+    _fields_ = [(n, C.c_void_p) for n in ("pose", "beta", "cam", "valid", "pose_out", "beta_out", "cam_out", "state")]
+
+
+SMOOTH_SHAPE_MODES = {"filter": 0, "mean": 1, "none": 2}     # HANDS_SMOOTH_SHAPE_*
+
+
+class SmoothCfg(C.Structure):
+    """hands_smooth_cfg (include/hands_hip.h): index 0 rotations, 1 shape, 2 camera."""
+    _fields_ = [("min_cutoff", C.c_double * 3), ("beta", C.c_double * 3), ("d_cutoff", C.c_double * 3), ("shape_mode", C.c_int)]
+
+
 class LossIn(C.Structure):
     """hands_loss_in (include/hands_hip.h): the first LOSS_N_MANDATORY pointers are mandatory, the rest come in groups."""
     _fields_ = [(n, C.c_void_p) for n in (
@@ -206,6 +219,7 @@ SIGNATURES = {
     "hands_eval_surface_metrics_f32": [C.POINTER(MeshEvalIn), _P, _P, _I, _I, C.POINTER(SurfEvalOut), _I, _I, _P],
     "hands_accel_error_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _P],
     "hands_eval_accel_metrics_f32": [C.POINTER(MeshEvalIn), _P, C.POINTER(AccelEvalOut), _I, _I, _F, _P],
+    "hands_smooth_mano_f32": [C.POINTER(SmoothSide), _I, _P, _I, _I, _F, C.POINTER(SmoothCfg), _P],
     "hands_loss_light_f32": [C.POINTER(LossIn), _I, _I, _I, _P, _P, _P, _P, _P],
     "hands_mano_pose_aa_f32": [C.POINTER(ManoConsts), _P, _P, _I, _P, _I, _P, _P, _I, _P],
     "hands_gt_targets_f32": [_P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _P],
@@ -228,7 +242,7 @@ SIGNATURES = {
 EXTRA_SYMBOLS = ("hands_abi_version", "hands_error_string", "hands_conv2d_workspace_floats", "hands_pack_conv3x3_winograd_floats", "hands_conv3x3_winograd_executed_macs",
                  "hands_pack_conv3x3_winograd4_floats", "hands_conv3x3_winograd4_executed_macs",
                  "hands_conv2d_streamk_workspace_bytes", "hands_stream_is_capturing", "hands_csrc_sha16", "hands_ceiling_mfma_f32", "hands_mesh_workspace_floats",
-                 "hands_loss_workspace_bytes")
+                 "hands_loss_workspace_bytes", "hands_smooth_state_bytes")
 
 ABI_VERSION = 5      # HANDS_ABI_VERSION of include/hands_hip.h this wrapper was written against
 _lib = None
@@ -276,6 +290,8 @@ def lib():
     h.hands_mesh_workspace_floats.argtypes = [C.c_int, C.c_int]
     h.hands_loss_workspace_bytes.restype = C.c_longlong
     h.hands_loss_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    h.hands_smooth_state_bytes.restype = C.c_longlong
+    h.hands_smooth_state_bytes.argtypes = []
     h.hands_error_string.restype = C.c_char_p
     h.hands_error_string.argtypes = [C.c_int]
     _lib = h

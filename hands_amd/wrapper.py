@@ -45,6 +45,9 @@ class HandsWrapper(nn.Module):
         self.metric_dict = ["mrrpe.rl", "mpjpe.ra", "mpjpe.pa.ra", "pix_err"]
         self.penetration_seal = True
         self.accel_fps = 30.0
+        # a hands_amd.TemporalSmoother here makes forward(..., "test") smooth the predictions over consecutive calls (One-Euro
+        # filter over the MANO parameters, re-posed) before the loss, the de-normalisation and the metrics; None: nothing changes
+        self.smoother = None
 
     def inference_pose(self, inputs, meta_info):
         pred = self.model(inputs, meta_info)
@@ -124,6 +127,11 @@ class HandsWrapper(nn.Module):
         """Forget the frames the "accel" metrics carry from one ``forward`` to the next (a new stream; ``accel_fps`` is read again)."""
         self.__dict__.pop("_accel_metrics_obj", None)
 
+    def reset_smoother(self):
+        """Start a new stream for ``smoother``, if there is one (its filter state and id dict are forgotten)."""
+        if self.smoother is not None:
+            self.smoother.reset()
+
     def forward(self, inputs, targets=None, meta_info=None, mode="test", compute_loss=False, loss_args=None):
         """GenericWrapper.forward without the training parts (src/models/generic/wrapper.py:77-164):
         GT preprocessing -> model -> [loss dict] -> 2-D de-normalisation -> metrics (``test``) / merged dict
@@ -134,7 +142,12 @@ class HandsWrapper(nn.Module):
         reference calls it (generic/wrapper.py:97-115) and ``test`` returns the weighted 0-dim values plus their sum
         under ``'loss'``; forward evaluation only -- ``mode="train"`` raises.  If the loss args switch
         ``use_render_seg_loss`` on and the model gave no ``render.r``, ``MANORenderer.render_masks`` fills
-        ``render.{r,l}`` into the predictions first."""
+        ``render.{r,l}`` into the predictions first.
+
+        With a ``TemporalSmoother`` in ``self.smoother``, a ``test`` call is a frame batch of its stream: the predictions are
+        replaced by ``smoother.update(...)`` right after the model call, a hand's frame being valid where
+        ``{right,left}_valid * is_valid`` of the targets is non-zero (every frame where the targets have no flags); loss,
+        masks and metrics -- "accel" among them -- then see the smoothed stream.  ``vis`` and ``extract`` are left alone."""
         if mode not in ("test", "extract", "vis"):
             raise NotImplementedError("hands_amd.HandsWrapper: the training mode (gradients, optimiser) is out of scope")
         inputs, targets, meta_info = xdict(inputs), xdict(targets or {}), xdict(meta_info)
@@ -142,6 +155,9 @@ class HandsWrapper(nn.Module):
         meta_info.overwrite("mano.faces.r", self.model.mano_r.faces)      # generic/wrapper.py:93-94
         meta_info.overwrite("mano.faces.l", self.model.mano_l.faces)
         pred = self.model(inputs, meta_info)
+        if self.smoother is not None and mode == "test":
+            flag = lambda k: targets[k] * targets["is_valid"] if k in targets and "is_valid" in targets else targets.get(k)
+            pred = self.smoother.update(pred, meta_info, valid_r=flag("right_valid"), valid_l=flag("left_valid"))
         loss_dict = {}
         if compute_loss:                                                   # generic/wrapper.py:97-115
             from .losses import compute_loss_light, mul_loss_dict, total_loss

@@ -783,6 +783,42 @@ int hands_eval_accel_metrics_f32(const hands_mesh_eval_in* in, const int32_t* se
                                  int V, float fps, hands_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Temporal smoothing on device (csrc/smooth.hip): the One-Euro filter (Casiez, Roussel, Vogel, CHI 2012) over the MANO
+ * parameters of hand-streams, rotations filtered on SO(3).  DESIGN.md section 7 "Temporal smoothing" is the specification
+ * (frame states, channel updates, Log and Exp with their branches); the reference has no counterpart.  One launch, one wave per
+ * (side, stream), time a serial loop inside the kernel; no allocation, no host synchronisation, no atomics.  fp32 in, fp64
+ * arithmetic, each output rounded once; a frame that is not filtered is copied bit for bit.
+ *
+ * Rows are T time steps of S parallel streams, row t * S + s: pose (T*S,16,3,3), beta (T*S,10), cam (T*S,3), valid (T*S) or
+ * NULL (every frame valid), seq_id (T*S) or NULL (one sequence), shared by the sides.  A frame is usable when valid != 0 and
+ * its 157 inputs are finite; an unusable frame, and the first usable frame after one or after a change of seq_id, pass through.
+ * state: NULL (start fresh, keep nothing) or S blocks of hands_smooth_state_bytes() bytes per side, 8-byte aligned, opaque,
+ * all zero before the first call; read at the start of the call and written back at its end, so a stream filtered in any split
+ * into calls gives the bits of one call.  Outputs must not overlap inputs, state or each other.
+ * shape_mode: the One-Euro filter, the running mean since the stream started, or the input.
+ * HANDS_EINVAL (nothing launched): NULL sides / cfg or a NULL pose, beta, cam or output of a side, nsides outside 1..2,
+ * T < 1, S < 1, fps / min_cutoff / d_cutoff not finite or <= 0, beta not finite or < 0, an unknown shape_mode.
+ * --------------------------------------------------------------------------------------------- */
+#define HANDS_SMOOTH_SHAPE_FILTER 0
+#define HANDS_SMOOTH_SHAPE_MEAN 1
+#define HANDS_SMOOTH_SHAPE_NONE 2
+
+typedef struct hands_smooth_side {
+  const float *pose, *beta, *cam, *valid;
+  float *pose_out, *beta_out, *cam_out;
+  void* state;
+} hands_smooth_side;
+
+typedef struct hands_smooth_cfg { /* index 0: rotations, 1: shape, 2: camera; cutoffs in Hz */
+  double min_cutoff[3], beta[3], d_cutoff[3];
+  int shape_mode;
+} hands_smooth_cfg;
+
+long long hands_smooth_state_bytes(void);
+int hands_smooth_mano_f32(const hands_smooth_side* sides, int nsides, const long long* seq_id, int T, int S, float fps,
+                          const hands_smooth_cfg* cfg, hands_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The validation loss dict on device, forward only (csrc/loss.hip): compute_loss_light of
  * src/callbacks/loss/loss_arctic_sf.py:20-206 (vector_loss / joints_loss / grasp_loss / render_loss of
  * src/utils/loss_modules.py:97-152) with the weighting and the total of src/models/generic/wrapper.py:19-23,100-115.
