@@ -15,7 +15,10 @@
 // and the projection of the point falls inside the triangle -- of the distance to the plane.  A face with a repeated index or
 // collinear vertices has an exactly zero normal in fp32 (ab x ab, products and differences of equal numbers: the library is
 // built with -ffp-contract=off, a fused multiply-add would leave its rounding residue there) and is the segment
-// or the point it collapses to without a special case; a zero edge has the parameter 0.
+// or the point it collapses to without a special case; a zero edge has the parameter 0.  A NEARLY degenerate face -- thin: the
+// sine of the angle at its first vertex is at most 1/64 -- takes "falls inside" and the plane distance in fp64 from its fp32
+// vertices, because the fp32 barycentrics of such a face are rounding noise (mesh_distance_device.h has the reasoning and the
+// threshold).  The flag belongs to the face, so a wave takes that branch together, once per face.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "hands_hip.h"
@@ -32,6 +35,19 @@ constexpr int NJ = 21;
 constexpr int NRED = 10;                         // widest reduction (K and var1)
 static_assert(HANDS_SURF_CHUNK % NT == 0 && MAXV % NT == 0, "a lane owns a whole number of queries");
 
+// One face against the lane's Q queries
+template <int Q, bool IDX, int THIN>
+__device__ __forceinline__ void scan_face(const Face& T, int f, const float (&p)[Q][3], float (&m)[Q], int (&mi)[Q]) {
+#pragma unroll
+  for (int k = 0; k < Q; ++k) {
+    const float d = tri_dist2<false, THIN>(T, p[k], nullptr);
+    if (d < m[k]) {
+      m[k] = d;
+      if (IDX) mi[k] = f;
+    }
+  }
+}
+
 // All faces against the lane's Q queries: m = smallest squared distance, mi = its face (strict <, ascending: the lowest index
 // wins an exact tie).  Every lane of the wave reads the same addresses.
 template <int Q, bool IDX>
@@ -41,14 +57,10 @@ __device__ __forceinline__ void scan_faces(const float* Vt, const unsigned short
     const unsigned i0 = Fc[3 * f];
     if (i0 == SKIP) continue;                    // the whole wave
     const Face T = make_face(Vt + 3 * i0, Vt + 3 * Fc[3 * f + 1], Vt + 3 * Fc[3 * f + 2]);
-#pragma unroll
-    for (int k = 0; k < Q; ++k) {
-      const float d = tri_dist2<false>(T, p[k], nullptr);
-      if (d < m[k]) {
-        m[k] = d;
-        if (IDX) mi[k] = f;
-      }
-    }
+    if (T.thin)                                  // the whole wave
+      scan_face<Q, IDX, 1>(T, f, p, m, mi);
+    else
+      scan_face<Q, IDX, 0>(T, f, p, m, mi);
   }
 }
 

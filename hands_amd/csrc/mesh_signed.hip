@@ -40,6 +40,24 @@ __host__ __device__ __forceinline__ float half_solid_angle(const float* v0, cons
   return num == 0.f && den == 0.f ? 0.f : atan2f(num, den);
 }
 
+// One face against the lane's queries: the distance, and the face's term of the winding number
+template <int THIN>
+__device__ __forceinline__ void signed_face(const Face& T, const float* v0, const float* v1, const float* v2, int f,
+                                            const float (&p)[QPL_SIGNED][3], float (&m)[QPL_SIGNED], int (&mi)[QPL_SIGNED],
+                                            float (&w)[QPL_SIGNED]) {
+#pragma unroll
+  for (int k = 0; k < QPL_SIGNED; ++k) {
+    const float d = tri_dist2<false, THIN>(T, p[k], nullptr);
+    if (d < m[k]) {
+      m[k] = d;
+      mi[k] = f;
+    }
+    // a face with an exactly zero normal subtends nothing; asked, it would return the rounding residue of a . (b x c)
+    // over a denominator that vanishes along its line.  The same for the whole wave
+    if (T.plane) w[k] += half_solid_angle(v0, v1, v2, p[k]);
+  }
+}
+
 // hands_mesh_closest_f32's walk with one more quantity per (query, face).  The winding number costs three square roots and an
 // atan2f per pair, about what the distance costs, so the walk stays bound by the vector pipe and a lane owns ONE query: 256 per
 // workgroup leave a 778-vertex hand 7 % of idle lanes where 512 leave 24 %, and with 36 KB of LDS four workgroups share a CU
@@ -78,17 +96,10 @@ __global__ void __launch_bounds__(NT) mesh_signed_kernel(const float* __restrict
       if (i0 == SKIP) continue;                  // the whole wave
       const float *v0 = Vt + 3 * i0, *v1 = Vt + 3 * Fc[3 * f + 1], *v2 = Vt + 3 * Fc[3 * f + 2];
       const Face T = make_face(v0, v1, v2);
-#pragma unroll
-      for (int k = 0; k < QPL_SIGNED; ++k) {
-        const float d = tri_dist2<false>(T, p[k], nullptr);
-        if (d < m[k]) {
-          m[k] = d;
-          mi[k] = f;
-        }
-        // a face with an exactly zero normal subtends nothing; asked, it would return the rounding residue of a . (b x c)
-        // over a denominator that vanishes along its line.  The same for the whole wave
-        if (T.plane) w[k] += half_solid_angle(v0, v1, v2, p[k]);
-      }
+      if (T.thin)                                // the whole wave: a thin face's plane test is fp64 (mesh_distance_device.h)
+        signed_face<1>(T, v0, v1, v2, f, p, m, mi, w);
+      else
+        signed_face<0>(T, v0, v1, v2, f, p, m, mi, w);
     }
 #pragma unroll
   for (int k = 0; k < QPL_SIGNED; ++k) {

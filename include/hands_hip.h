@@ -690,7 +690,11 @@ int hands_eval_mesh_metrics_f32(const hands_mesh_eval_in* in, const hands_mesh_e
  *   dist[b,p]      Euclidean distance from the point to the closed triangle, minimised over the faces: squared distances and
  *                  their comparison in fp32, a strict < in ascending face order (the lowest index wins an exact tie), one
  *                  square root at the end.  Point to triangle: the minimum of the three clamped segment distances and, where
- *                  the normal is not zero and the projection falls inside, the distance to the plane;
+ *                  the normal is not zero and the projection falls inside, the distance to the plane.  "Inside" and the plane
+ *                  distance are fp32 too, except for a THIN face -- the sine of the angle at its first vertex is at most 1/64,
+ *                  which slivers and caps are from every vertex -- where fp32 barycentrics are rounding noise: they are
+ *                  fp64 from the fp32 vertices there, good down to a height of 1e-6 of the longest edge
+ *                  (csrc/mesh_distance_device.h);
  *   face_idx[b,p]  (or NULL) that face;  closest[b,p] (or NULL) the closest point on it.
  *   A degenerate face -- a repeated vertex index, collinear vertices -- is the segment or the point it collapses to.  A face with
  *   an index outside [0, V) or with a non-finite vertex is skipped.  No face left, or F == 0: dist +inf, face_idx -1, closest
