@@ -22,6 +22,7 @@ from .penetration import (seal_mesh, apply_seal, signed_distance_to_mesh, interh
                           intersection_volume)
 from .temporal import accel_error, evaluate_accel_metrics, AccelMetrics  # noqa: F401
 from .smoothing import SmoothConfig, smooth_mano_params, smooth_predictions, TemporalSmoother  # noqa: F401
+from .fitting import FitConfig, fit_mano, fit_mano_hands, fit_targets  # noqa: F401
 
 __all__ = ["HandsLight", "DEFAULT_ARGS", "ManoHeadsPlan", "HAMER", "HAMER_DEFAULT_ARGS", "HandOccNet", "HANDOCC_DEFAULT_ARGS", "xdict", "prefix_dict", "ManoAsset", "synthetic_mano_asset",
            "build_mano_asset", "apply_recipe", "synthetic_inputs", "HandsFrontEnd", "GraphedForward", "HandsWrapper",
@@ -30,4 +31,5 @@ __all__ = ["HandsLight", "DEFAULT_ARGS", "ManoHeadsPlan", "HAMER", "HAMER_DEFAUL
            "evaluate_surface_metrics", "closest_on_mesh", "interhand_field", "evaluate_penetration_metrics", "seal_mesh", "apply_seal",
            "signed_distance_to_mesh", "interhand_penetration", "penetration_grid", "intersection_volume",
            "accel_error", "evaluate_accel_metrics", "AccelMetrics",
-           "SmoothConfig", "smooth_mano_params", "smooth_predictions", "TemporalSmoother"]
+           "SmoothConfig", "smooth_mano_params", "smooth_predictions", "TemporalSmoother",
+           "FitConfig", "fit_mano", "fit_mano_hands", "fit_targets"]

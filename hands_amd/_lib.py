@@ -106,6 +106,23 @@ class SmoothCfg(C.Structure):
     _fields_ = [("min_cutoff", C.c_double * 3), ("beta", C.c_double * 3), ("d_cutoff", C.c_double * 3), ("shape_mode", C.c_int)]
 
 
+class ManoFitConsts(C.Structure):
+    """hands_mano_fit_consts (include/hands_hip.h): the three joint constants of ManoConsts and the tip pack."""
+    _fields_ = [(n, C.c_void_p) for n in ("pose_mean", "J_template", "J_shapedirs", "tip_v_template", "tip_shapedirs",
+                                          "tip_lbs_weights", "tip_posedirs")]
+
+
+class ManoFitSide(C.Structure):
+    """hands_mano_fit_side (include/hands_hip.h): one hand of a hands_mano_fit_f32 call; weights, valid and init_* may be NULL."""
+    _fields_ = [("consts", ManoFitConsts)] + [(n, C.c_void_p) for n in (
+        "joints", "weights", "valid", "init_pose", "init_beta", "init_transl", "pose", "beta", "transl", "rmse", "steps")]
+
+
+class FitCfg(C.Structure):
+    """hands_fit_cfg (include/hands_hip.h)."""
+    _fields_ = [("iters", C.c_int), ("lambda_beta", C.c_double), ("lambda_pose", C.c_double), ("mu0", C.c_double)]
+
+
 class LossIn(C.Structure):
     """hands_loss_in (include/hands_hip.h): the first LOSS_N_MANDATORY pointers are mandatory, the rest come in groups."""
     _fields_ = [(n, C.c_void_p) for n in (
@@ -220,6 +237,7 @@ SIGNATURES = {
     "hands_accel_error_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _P],
     "hands_eval_accel_metrics_f32": [C.POINTER(MeshEvalIn), _P, C.POINTER(AccelEvalOut), _I, _I, _F, _P],
     "hands_smooth_mano_f32": [C.POINTER(SmoothSide), _I, _P, _I, _I, _F, C.POINTER(SmoothCfg), _P],
+    "hands_mano_fit_f32": [C.POINTER(ManoFitSide), _I, C.POINTER(FitCfg), _I, _P],
     "hands_loss_light_f32": [C.POINTER(LossIn), _I, _I, _I, _P, _P, _P, _P, _P],
     "hands_mano_pose_aa_f32": [C.POINTER(ManoConsts), _P, _P, _I, _P, _I, _P, _P, _I, _P],
     "hands_gt_targets_f32": [_P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _P],

@@ -1,0 +1,551 @@
+// fit.hip -- MANO fitting on device (hands_mano_fit_f32 of include/hands_hip.h): a Levenberg-Marquardt fit of the 16 rotations
+// of the full pose, the shape and a translation (61 unknowns) to 21 3-D joints.  DESIGN.md section 7 "MANO fitting" is the
+// specification, tests/fit_ref.py its fp64 restatement; the reference has no fitter.
+// One launch fits every hand of a call: grid (B, n_sides), one workgroup of four waves per hand, the hands independent.  fp32 in,
+// fp64 arithmetic, one rounding per output.  A hand's problem lives in LDS (61 KB): the data rows of the Jacobian (63 x 61), the
+// lower triangle of H = J^T J with the priors and the damping on its diagonal -- the Cholesky factor overwrites it, H is formed
+// again in every iteration --, the two states (current, candidate) and what forward kinematics leaves of the current one.
+// The work of an iteration spreads over the 256 lanes: the 3 x 3 blocks of the Jacobian (one item a lane and pass), the 1891
+// entries of H (a dot product of 63 each), the column scaling and the trailing update of the Cholesky factorisation; the two
+// triangular solves run in wave 0 with the right-hand side in registers and the pivot value passed by shuffle.
+// H is formed on the vector pipe, not with v_mfma_f64: it is 117 k multiply-adds of an iteration whose length the 61
+// dependent Cholesky columns (two barriers each) set, so the matrix pipe would shorten what is not the critical path, at the
+// cost of a second operand layout of J.
+// The iteration runs exactly `iters` times; the only data-dependent branch is accept / reject, uniform in the workgroup.  No
+// atomics, no inter-workgroup synchronisation, no allocation; per-lane arrays are indexed by constants only (no scratch).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "hands_hip.h"
+#include "common.h"
+#include "procrustes_device.h"
+
+namespace {
+
+constexpr int NT = 256;                          // lanes of a workgroup
+constexpr int NU = 61;                           // unknowns: 16 x 3 rotation increments, 10 shape, 3 translation
+constexpr int NR = 63;                           // data rows: 21 joints x 3
+constexpr int HP = NU * (NU + 1) / 2;            // the packed lower triangle: entry (a, b <= a) at a (a + 1) / 2 + b
+constexpr int UB = 48, UT = 58;                  // first shape column, first translation column
+constexpr double PI = 3.14159265358979323846;
+constexpr double MU_MIN = 1e-9, MU_MAX = 1e6;
+
+struct Lds {
+  double J[NR * NU];
+  double H[HP];
+  double diag[NU], g[NU], d[NU];                 // the pivots of the factor, J^T r, the step
+  double R[2][144], beta[2][10], t[2][3];        // state 0: current, 1: candidate
+  double M[144];                                 // Exp(pose_mean_j)
+  // of the state evaluate() saw last
+  double Jr[48], Q[144], p[48], vp[15], x[240], A[45], joints[63], lg[45], r[NR];
+  double dp[480];                                // d p_i / d beta, (16, 3, 10)
+  double y[NR], w[21], sw[21];
+  double c[2];                                   // cost, and its data part sum_k w_k |j_k + t - y_k|^2
+};
+
+// D = A^T B, row-major 3x3
+__device__ __forceinline__ void mul_tn(const double* A, const double* B, double* D) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) D[3 * i + j] = (A[i] * B[j] + A[3 + i] * B[3 + j]) + A[6 + i] * B[6 + j];
+}
+
+__device__ __forceinline__ void mul_nn(const double* A, const double* B, double* D) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) D[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
+}
+
+// Log and Exp on SO(3) with the branches of DESIGN.md section 7 (the arithmetic of smooth.hip)
+__device__ __forceinline__ void log_so3(const double* D, double* w) {
+  const double v0 = 0.5 * (D[7] - D[5]), v1 = 0.5 * (D[2] - D[6]), v2 = 0.5 * (D[3] - D[1]);
+  const double s = sqrt((v0 * v0 + v1 * v1) + v2 * v2);
+  const double c = 0.5 * (((D[0] + D[4]) + D[8]) - 1.0);
+  if (s >= 1e-9) {
+    const double k = atan2(s, c) / s;
+    w[0] = v0 * k; w[1] = v1 * k; w[2] = v2 * k;
+  } else if (c >= 0.0) {
+    w[0] = v0; w[1] = v1; w[2] = v2;
+  } else {                                       // a half turn: the axis from the symmetric part
+    double u0 = sqrt(fmax(0.0, (D[0] - c) / (1.0 - c)));
+    double u1 = sqrt(fmax(0.0, (D[4] - c) / (1.0 - c)));
+    double u2 = sqrt(fmax(0.0, (D[8] - c) / (1.0 - c)));
+    const double s01 = D[1] + D[3], s02 = D[2] + D[6], s12 = D[5] + D[7];
+    if (u0 >= u1 && u0 >= u2) {
+      u1 = s01 < 0.0 ? -u1 : u1;
+      u2 = s02 < 0.0 ? -u2 : u2;
+    } else if (u1 >= u2) {
+      u0 = s01 < 0.0 ? -u0 : u0;
+      u2 = s12 < 0.0 ? -u2 : u2;
+    } else {
+      u0 = s02 < 0.0 ? -u0 : u0;
+      u1 = s12 < 0.0 ? -u1 : u1;
+    }
+    const double k = PI / sqrt((u0 * u0 + u1 * u1) + u2 * u2);
+    w[0] = u0 * k; w[1] = u1 * k; w[2] = u2 * k;
+  }
+}
+
+__device__ __forceinline__ void exp_so3(const double* w, double* E) {
+  const double theta = sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
+  const double K[9] = {0.0, -w[2], w[1], w[2], 0.0, -w[0], -w[1], w[0], 0.0};
+  double K2[9];
+  mul_nn(K, K, K2);
+  double a = 1.0, b = 0.5;
+  if (theta >= 1e-6) {
+    double sn, cs;
+    sincos(theta, &sn, &cs);
+    a = sn / theta;
+    b = (1.0 - cs) / (theta * theta);
+  }
+#pragma unroll
+  for (int i = 0; i < 9; ++i) E[i] = ((i % 4 == 0 ? 1.0 : 0.0) + a * K[i]) + b * K2[i];
+}
+
+// joint i is joint j or one of its descendants (wrist 0, finger f = joints 1 + 3 f .. 3 + 3 f)
+__device__ __forceinline__ bool at_or_below(int j, int i) { return j == 0 || (i >= j && (i - 1) / 3 == (j - 1) / 3); }
+__device__ __forceinline__ int parent_of(int i) { return (i - 1) % 3 == 0 ? 0 : i - 1; }      // i >= 1
+
+// Forward kinematics, the five tips, the residual and the cost of state s.  Every lane of the workgroup calls it.
+__device__ void evaluate(Lds& S, const hands_mano_fit_consts& C, int s, double lb, double lp, int tid) {
+  const double* R = S.R[s];
+  const double* be = S.beta[s];
+  if (tid < 48) {                                // rest joints of this shape
+    double a = (double)C.J_template[tid];
+#pragma unroll
+    for (int l = 0; l < 10; ++l) a += (double)C.J_shapedirs[tid * 10 + l] * be[l];
+    S.Jr[tid] = a;
+  } else if (tid >= 64 && tid < 79) {            // the tips before skinning: template, shape and pose blend shapes
+    const int mc = tid - 64;
+    double a = (double)C.tip_v_template[mc];
+#pragma unroll
+    for (int l = 0; l < 10; ++l) a += (double)C.tip_shapedirs[mc * 10 + l] * be[l];
+#pragma unroll 5
+    for (int f = 0; f < 135; ++f) a += (R[9 + f] - ((f % 9) % 4 == 0 ? 1.0 : 0.0)) * (double)C.tip_posedirs[f * 15 + mc];
+    S.vp[mc] = a;
+  } else if (tid >= 128 && tid < 143) {          // the pose prior: Log(M_j^T R_j), j = 1..15
+    const int j = tid - 127;
+    double D[9], w[3];
+    mul_tn(S.M + 9 * j, R + 9 * j, D);
+    log_so3(D, w);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) S.lg[3 * (j - 1) + c] = w[c];
+  }
+  __syncthreads();
+  if (tid < 5) {                                 // a finger's chain from the wrist
+    double Qa[9], pa[3];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) Qa[i] = R[i];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) pa[c] = S.Jr[c];
+#pragma unroll
+    for (int n = 0; n < 3; ++n) {
+      const int i = 1 + 3 * tid + n, a = n == 0 ? 0 : i - 1;
+      double Qi[9], pi[3];
+      mul_nn(Qa, R + 9 * i, Qi);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const double e0 = S.Jr[3 * i] - S.Jr[3 * a], e1 = S.Jr[3 * i + 1] - S.Jr[3 * a + 1], e2 = S.Jr[3 * i + 2] - S.Jr[3 * a + 2];
+        pi[c] = pa[c] + ((Qa[3 * c] * e0 + Qa[3 * c + 1] * e1) + Qa[3 * c + 2] * e2);
+      }
+#pragma unroll
+      for (int k = 0; k < 9; ++k) S.Q[9 * i + k] = Qa[k] = Qi[k];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) S.p[3 * i + c] = pa[c] = pi[c];
+    }
+  } else if (tid == 5) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) S.Q[k] = R[k];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) S.p[c] = S.Jr[c];
+  }
+  __syncthreads();
+  for (int it = tid; it < 240 + 45; it += NT) {
+    if (it < 240) {                              // x[m][i]: tip m as joint i carries it
+      const int m = it / 48, i = (it % 48) / 3, c = it % 3;
+      const double* q = S.Q + 9 * i + 3 * c;
+      S.x[it] = S.p[3 * i + c] + ((q[0] * (S.vp[3 * m] - S.Jr[3 * i]) + q[1] * (S.vp[3 * m + 1] - S.Jr[3 * i + 1])) +
+                                  q[2] * (S.vp[3 * m + 2] - S.Jr[3 * i + 2]));
+    } else {                                     // A[m] = sum_i W_mi Q_i
+      const int m = (it - 240) / 9, ab = (it - 240) % 9;
+      double a = 0.0;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) a += (double)C.tip_lbs_weights[m * 16 + i] * S.Q[9 * i + ab];
+      S.A[it - 240] = a;
+    }
+  }
+  __syncthreads();
+  if (tid < 15) {
+    const int m = tid / 3, c = tid % 3;
+    double a = 0.0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) a += (double)C.tip_lbs_weights[m * 16 + i] * S.x[m * 48 + 3 * i + c];
+    S.joints[48 + tid] = a;
+  } else if (tid >= 64 && tid < 112) {
+    S.joints[tid - 64] = S.p[tid - 64];
+  }
+  __syncthreads();
+  if (tid < 64) {                                // residual and cost: wave 0
+    double r = 0.0;
+    if (tid < NR) {
+      const int k = tid / 3;
+      r = S.w[k] > 0.0 ? S.sw[k] * ((S.joints[tid] + S.t[s][tid % 3]) - S.y[tid]) : 0.0;      // selected, not multiplied
+      S.r[tid] = r;
+    }
+    double data = r * r;
+    double all = data + (tid < 10 ? lb * (be[tid] * be[tid]) : 0.0) + (tid < 45 ? lp * (S.lg[tid] * S.lg[tid]) : 0.0);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      data += __shfl_xor(data, o);
+      all += __shfl_xor(all, o);
+    }
+    if (tid == 0) {
+      S.c[0] = all;
+      S.c[1] = data;
+    }
+  }
+  __syncthreads();
+}
+
+// The data rows of the Jacobian at the state evaluate() saw last (state s), g = J^T r and the damped H, priors included.
+__device__ void linearise(Lds& S, const hands_mano_fit_consts& C, int s, double lb, double lp, double mu, int tid) {
+  if (tid < 10) {                                // d p_i / d beta_l along the chain, l = tid
+    for (int i = 0; i < 16; ++i) {
+      const int a = i == 0 ? 0 : parent_of(i);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        double v = (double)C.J_shapedirs[(3 * i + c) * 10 + tid];
+        if (i > 0) {
+          const double e0 = (double)C.J_shapedirs[(3 * i) * 10 + tid] - (double)C.J_shapedirs[(3 * a) * 10 + tid];
+          const double e1 = (double)C.J_shapedirs[(3 * i + 1) * 10 + tid] - (double)C.J_shapedirs[(3 * a + 1) * 10 + tid];
+          const double e2 = (double)C.J_shapedirs[(3 * i + 2) * 10 + tid] - (double)C.J_shapedirs[(3 * a + 2) * 10 + tid];
+          const double* q = S.Q + 9 * a + 3 * c;
+          v = S.dp[(3 * a + c) * 10 + tid] + ((q[0] * e0 + q[1] * e1) + q[2] * e2);
+        }
+        S.dp[(3 * i + c) * 10 + tid] = v;
+      }
+    }
+  }
+  __syncthreads();
+  for (int it = tid; it < 336 + 210 + NR; it += NT) {
+    if (it < 336) {                              // d point k / d delta_j, a 3 x 3 block
+      const int k = it / 16, j = it % 16;
+      const double* Qj = S.Q + 9 * j;
+      double B[9], v[3] = {0.0, 0.0, 0.0};
+      bool moves = true;
+      if (k < 16) {
+        moves = k != j && at_or_below(j, k);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = S.p[3 * k + c] - S.p[3 * j + c];
+      } else {
+        const int m = k - 16;
+#pragma unroll 1
+        for (int i = 0; i < 16; ++i)
+          if (at_or_below(j, i)) {
+            const double wi = (double)C.tip_lbs_weights[m * 16 + i];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c] += wi * (S.x[m * 48 + 3 * i + c] - S.p[3 * j + c]);
+          }
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {              // column c of -[v]x Q_j = (column c of Q_j) x v
+        const double q0 = Qj[c], q1 = Qj[3 + c], q2 = Qj[6 + c];
+        B[c] = moves ? q1 * v[2] - q2 * v[1] : 0.0;
+        B[3 + c] = moves ? q2 * v[0] - q0 * v[2] : 0.0;
+        B[6 + c] = moves ? q0 * v[1] - q1 * v[0] : 0.0;
+      }
+      if (k >= 16 && j >= 1) {                   // the pose blend shapes: (sum_i W_i Q_i) posedirs_tip vec(R_j [e_a]x)
+        const int m = k - 16;
+        const double* Rj = S.R[s] + 9 * j;
+        const float* pd = C.tip_posedirs + 9 * (j - 1) * 15 + 3 * m;
+        const double* Am = S.A + 9 * m;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+          double dR[9];
+#pragma unroll
+          for (int r = 0; r < 3; ++r) {          // R [e_a]x: columns (0, R2, -R1), (-R2, 0, R0), (R1, -R0, 0)
+            dR[3 * r] = a == 0 ? 0.0 : (a == 1 ? -Rj[3 * r + 2] : Rj[3 * r + 1]);
+            dR[3 * r + 1] = a == 0 ? Rj[3 * r + 2] : (a == 1 ? 0.0 : -Rj[3 * r]);
+            dR[3 * r + 2] = a == 0 ? -Rj[3 * r + 1] : (a == 1 ? Rj[3 * r] : 0.0);
+          }
+          double u[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+          for (int f = 0; f < 9; ++f)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) u[c] += dR[f] * (double)pd[f * 15 + c];
+#pragma unroll
+          for (int r = 0; r < 3; ++r) B[3 * r + a] += (Am[3 * r] * u[0] + Am[3 * r + 1] * u[1]) + Am[3 * r + 2] * u[2];
+        }
+      }
+      const bool on = S.w[k] > 0.0;
+      const double sw = S.sw[k];
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) S.J[(3 * k + r) * NU + 3 * j + c] = on ? sw * B[3 * r + c] : 0.0;
+    } else if (it < 336 + 210) {                 // d point k / d beta_l
+      const int k = (it - 336) / 10, l = (it - 336) % 10;
+      double v[3];
+      if (k < 16) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = S.dp[(3 * k + c) * 10 + l];
+      } else {
+        const int m = k - 16;
+        v[0] = v[1] = v[2] = 0.0;
+#pragma unroll 1
+        for (int i = 0; i < 16; ++i) {
+          const double wi = (double)C.tip_lbs_weights[m * 16 + i];
+          const double e0 = (double)C.tip_shapedirs[(3 * m) * 10 + l] - (double)C.J_shapedirs[(3 * i) * 10 + l];
+          const double e1 = (double)C.tip_shapedirs[(3 * m + 1) * 10 + l] - (double)C.J_shapedirs[(3 * i + 1) * 10 + l];
+          const double e2 = (double)C.tip_shapedirs[(3 * m + 2) * 10 + l] - (double)C.J_shapedirs[(3 * i + 2) * 10 + l];
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const double* q = S.Q + 9 * i + 3 * c;
+            v[c] += wi * (((q[0] * e0 + q[1] * e1) + q[2] * e2) + S.dp[(3 * i + c) * 10 + l]);
+          }
+        }
+      }
+      const bool on = S.w[k] > 0.0;
+      const double sw = S.sw[k];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) S.J[(3 * k + c) * NU + UB + l] = on ? sw * v[c] : 0.0;
+    } else {                                     // d / d t = I
+      const int row = it - (336 + 210), k = row / 3, c = row % 3;
+      const bool on = S.w[k] > 0.0;
+      const double sw = S.sw[k];
+#pragma unroll
+      for (int cc = 0; cc < 3; ++cc) S.J[row * NU + UT + cc] = (on && cc == c) ? sw : 0.0;
+    }
+  }
+  __syncthreads();
+  if (tid < NU) {                                // g = J^T r, the priors with d Log / d delta = I
+    double a = 0.0;
+#pragma unroll 3
+    for (int r = 0; r < NR; ++r) a += S.J[r * NU + tid] * S.r[r];
+    if (tid >= 3 && tid < UB) a += lp * S.lg[tid - 3];
+    if (tid >= UB && tid < UT) a += lb * S.beta[s][tid - UB];
+    S.g[tid] = a;
+  }
+  for (int e = tid; e < HP; e += NT) {           // H + mu diag H, lower triangle
+    int a = (int)((sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);
+    if (a * (a + 1) / 2 > e) --a;
+    if ((a + 1) * (a + 2) / 2 <= e) ++a;
+    const int b = e - a * (a + 1) / 2;
+    double h = 0.0;
+#pragma unroll 3
+    for (int r = 0; r < NR; ++r) h += S.J[r * NU + a] * S.J[r * NU + b];
+    if (a == b) {
+      if (a >= 3 && a < UB) h += lp;
+      if (a >= UB && a < UT) h += lb;
+      h += mu * h;
+    }
+    S.H[e] = h;
+  }
+  __syncthreads();
+}
+
+// Cholesky of the packed lower triangle in place (the pivots' roots go to S.diag), then L L^T d = -g.  -> false at a pivot that
+// is not positive; the same value on every lane.
+__device__ bool solve(Lds& S, int tid) {
+  bool ok = true;
+  const int i = tid & 63, jg = tid >> 6;
+  for (int k = 0; k < NU; ++k) {
+    const double piv = S.H[k * (k + 1) / 2 + k];
+    ok = ok && piv > 0.0;
+    const double dd = sqrt(piv > 0.0 ? piv : 1.0);
+    if (tid > k && tid < NU) S.H[tid * (tid + 1) / 2 + k] /= dd;       // the pivot itself stays: other lanes still read it
+    if (tid == 0) S.diag[k] = dd;
+    __syncthreads();
+    if (i > k && i < NU) {
+      const double lik = S.H[i * (i + 1) / 2 + k];
+      for (int j = k + 1 + jg; j <= i; j += 4) S.H[i * (i + 1) / 2 + j] -= lik * S.H[j * (j + 1) / 2 + k];
+    }
+    __syncthreads();
+  }
+  if (tid < 64) {                                // wave 0: forward, then backward substitution; lane u holds entry u
+    const int u = tid < NU ? tid : NU - 1;
+    double b = tid < NU ? -S.g[tid] : 0.0;
+    for (int k = 0; k < NU; ++k) {
+      const double yk = __shfl(b, k) / S.diag[k];
+      if (tid == k) b = yk;
+      if (tid > k && tid < NU) b -= S.H[u * (u + 1) / 2 + k] * yk;
+    }
+    for (int k = NU - 1; k >= 0; --k) {
+      const double xk = __shfl(b, k) / S.diag[k];
+      if (tid == k) b = xk;
+      if (tid < k) b -= S.H[k * (k + 1) / 2 + u] * xk;
+    }
+    if (tid < NU) S.d[tid] = b;
+  }
+  __syncthreads();
+  return ok;
+}
+
+struct Sides {
+  hands_mano_fit_side s[2];
+};
+
+__global__ void __launch_bounds__(NT) mano_fit_kernel(Sides sides, hands_fit_cfg cfg) {
+  __shared__ Lds S;
+  const int tid = threadIdx.x;
+  const long long b = blockIdx.x;
+  const hands_mano_fit_side& sd = sides.s[blockIdx.y];
+  const hands_mano_fit_consts& C = sd.consts;
+  const double lb = cfg.lambda_beta, lp = cfg.lambda_pose;
+
+  // the target: a joint of weight 0 (or of a weight that is no number) is never read
+  bool sel = false, bad = false;
+  if (tid < 21) {
+    const double w = sd.weights ? (double)sd.weights[b * 21 + tid] : 1.0;
+    sel = w > 0.0;
+    S.w[tid] = sel ? w : 0.0;
+    S.sw[tid] = sel ? sqrt(w) : 0.0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float v = sel ? sd.joints[(b * 21 + tid) * 3 + c] : 0.f;
+      bad = bad || !isfinite(v);
+      S.y[3 * tid + c] = (double)v;
+    }
+  }
+  if (tid >= 64 && tid < 80) {
+    const int j = tid - 64;
+    const double w[3] = {(double)C.pose_mean[3 * j], (double)C.pose_mean[3 * j + 1], (double)C.pose_mean[3 * j + 2]};
+    double E[9];
+    exp_so3(w, E);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) S.M[9 * j + k] = E[k];
+  }
+  if (sd.init_pose && tid < 157) {               // a caller's initial state
+    const float v = tid < 144 ? sd.init_pose[b * 144 + tid] : (tid < 154 ? sd.init_beta[b * 10 + tid - 144] : sd.init_transl[b * 3 + tid - 154]);
+    bad = bad || !isfinite(v);
+    if (tid < 144) S.R[0][tid] = (double)v;
+    else if (tid < 154) S.beta[0][tid - 144] = (double)v;
+    else S.t[0][tid - 154] = (double)v;
+  }
+  const int nsel = __syncthreads_count(sel);
+  const bool any_bad = __syncthreads_or(bad);
+  const bool fitted = (sd.valid ? sd.valid[b] != 0.f : true) && nsel >= 4 && !any_bad;
+  if (!fitted) {                                 // the whole workgroup leaves: pose (I, M_1..M_15), zeros, NaN, no step
+    if (tid < 144) sd.pose[b * 144 + tid] = (float)S.M[tid];
+    else if (tid < 154) sd.beta[b * 10 + tid - 144] = 0.f;
+    else if (tid < 157) sd.transl[b * 3 + tid - 154] = 0.f;
+    else if (tid == 157) sd.rmse[b] = __builtin_nanf("");
+    else if (tid == 158) sd.steps[b] = 0;
+    return;
+  }
+
+  if (!sd.init_pose) {                           // the rest hand, aligned rigidly to the target
+    if (tid < 144) S.R[0][tid] = S.M[tid];
+    else if (tid < 154) S.beta[0][tid - 144] = 0.0;
+    else if (tid < 157) S.t[0][tid - 154] = 0.0;
+    __syncthreads();
+    evaluate(S, C, 0, lb, lp, tid);
+    if (tid == 0) {
+      double sw = 0.0, mx[3] = {0.0, 0.0, 0.0}, my[3] = {0.0, 0.0, 0.0};
+      for (int k = 0; k < 21; ++k)
+        if (S.w[k] > 0.0) {
+          sw += S.w[k];
+          for (int c = 0; c < 3; ++c) {
+            mx[c] += S.w[k] * S.joints[3 * k + c];
+            my[c] += S.w[k] * S.y[3 * k + c];
+          }
+        }
+      for (int c = 0; c < 3; ++c) { mx[c] /= sw; my[c] /= sw; }
+      double K[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, var1 = 0.0;
+      for (int k = 0; k < 21; ++k)
+        if (S.w[k] > 0.0)
+          for (int a = 0; a < 3; ++a) {
+            const double x1 = S.joints[3 * k + a] - mx[a];
+            var1 += S.w[k] * x1 * x1;
+            for (int c = 0; c < 3; ++c) K[a][c] += S.w[k] * x1 * (S.y[3 * k + c] - my[c]);
+          }
+      double Rm[3][3], scale;
+      procrustes_solve(K, var1, Rm, &scale);     // the scale is not used: the alignment is rigid
+      for (int a = 0; a < 3; ++a) {              // MANO turns about the wrist joint J_0: y ~ Rm (x - J_0) + J_0 + t
+        const double e0 = mx[0] - S.Jr[0], e1 = mx[1] - S.Jr[1], e2 = mx[2] - S.Jr[2];
+        S.t[0][a] = (my[a] - ((Rm[a][0] * e0 + Rm[a][1] * e1) + Rm[a][2] * e2)) - S.Jr[a];
+        for (int c = 0; c < 3; ++c) S.R[0][3 * a + c] = Rm[a][c];
+      }
+    }
+  }
+  __syncthreads();
+
+  // `fresh`: what evaluate() left in LDS belongs to the current state -- after an accepted step it does, the candidate having
+  // become the current state, and the evaluation is not repeated (it would give the same bits)
+  double mu = cfg.mu0, c0 = 0.0;
+  int steps = 0;
+  bool fresh = false;
+  for (int it = 0; it < cfg.iters; ++it) {
+    if (!fresh) {
+      evaluate(S, C, 0, lb, lp, tid);
+      c0 = S.c[0];
+    }
+    linearise(S, C, 0, lb, lp, mu, tid);
+    const bool ok = solve(S, tid);
+    if (tid < 16) {                              // the candidate: R_j Exp(delta_j), beta + delta_beta, t + delta_t
+      const double w[3] = {S.d[3 * tid], S.d[3 * tid + 1], S.d[3 * tid + 2]};
+      double E[9], Rn[9];
+      exp_so3(w, E);
+      mul_nn(S.R[0] + 9 * tid, E, Rn);
+#pragma unroll
+      for (int k = 0; k < 9; ++k) S.R[1][9 * tid + k] = Rn[k];
+    } else if (tid >= 64 && tid < 74) {
+      S.beta[1][tid - 64] = S.beta[0][tid - 64] + S.d[UB + tid - 64];
+    } else if (tid >= 74 && tid < 77) {
+      S.t[1][tid - 74] = S.t[0][tid - 74] + S.d[UT + tid - 74];
+    }
+    __syncthreads();
+    evaluate(S, C, 1, lb, lp, tid);
+    const double c1 = S.c[0];
+    const bool accept = ok && c1 < c0;           // strict, false for NaN; the same on every lane
+    fresh = accept;
+    if (accept) {
+      c0 = c1;
+      if (tid < 144) S.R[0][tid] = S.R[1][tid];
+      else if (tid < 154) S.beta[0][tid - 144] = S.beta[1][tid - 144];
+      else if (tid < 157) S.t[0][tid - 154] = S.t[1][tid - 154];
+      mu = fmax(mu / 3.0, MU_MIN);
+      ++steps;
+    } else {
+      mu = fmin(5.0 * mu, MU_MAX);
+    }
+    __syncthreads();
+  }
+  if (!fresh) evaluate(S, C, 0, lb, lp, tid);
+
+  if (tid < 144) sd.pose[b * 144 + tid] = (float)S.R[0][tid];
+  else if (tid < 154) sd.beta[b * 10 + tid - 144] = (float)S.beta[0][tid - 144];
+  else if (tid < 157) sd.transl[b * 3 + tid - 154] = (float)S.t[0][tid - 154];
+  else if (tid == 157) {
+    double sw = 0.0;
+    for (int k = 0; k < 21; ++k) sw += S.w[k];
+    sd.rmse[b] = (float)sqrt(S.c[1] / sw);
+  } else if (tid == 158) {
+    sd.steps[b] = steps;
+  }
+}
+
+bool non_negative(double v) { return isfinite(v) && v >= 0.0; }
+
+}  // namespace
+
+extern "C" int hands_mano_fit_f32(const hands_mano_fit_side* sides, int n_sides, const hands_fit_cfg* cfg, int B,
+                                  hands_stream_t stream) {
+  if (!sides || !cfg || n_sides < 1 || n_sides > 2 || B <= 0 || cfg->iters < 0) return HANDS_EINVAL;
+  if (!non_negative(cfg->lambda_beta) || !non_negative(cfg->lambda_pose) || !non_negative(cfg->mu0)) return HANDS_EINVAL;
+  Sides k;
+  for (int i = 0; i < 2; ++i) {
+    k.s[i] = sides[i < n_sides ? i : 0];
+    const hands_mano_fit_side& d = k.s[i];
+    const hands_mano_fit_consts& c = d.consts;
+    if (!c.pose_mean || !c.J_template || !c.J_shapedirs || !c.tip_v_template || !c.tip_shapedirs || !c.tip_lbs_weights ||
+        !c.tip_posedirs)
+      return HANDS_EINVAL;
+    if (!d.joints || !d.pose || !d.beta || !d.transl || !d.rmse || !d.steps) return HANDS_EINVAL;
+    const int given = (d.init_pose != nullptr) + (d.init_beta != nullptr) + (d.init_transl != nullptr);
+    if (given != 0 && given != 3) return HANDS_EINVAL;
+  }
+  hipLaunchKernelGGL(mano_fit_kernel, dim3(B, n_sides), dim3(NT), 0, (hipStream_t)stream, k, *cfg);
+  HANDS_LAUNCH_CHECK();
+}

@@ -169,9 +169,13 @@ def pack_mano(asset: ManoAsset, device):
     blend = PackedConv(torch.from_numpy(bw).to(device), torch.from_numpy(bb).to(device), 160, 2336, 1, 1, 1, 0, 160,
                        macs_per_pixel=2334 * 145)
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    tips = list(TIP_IDS)
     return {
         "pose_mean": t(pose_mean), "J_template": t(J_template), "J_shapedirs": t(J_shapedirs),
         "lbs_weights": t(asset.lbs_weights.astype(np.float32)),
         "tip_ids": t(np.asarray(TIP_IDS, np.int32)), "blend": blend,
         "faces": torch.from_numpy(asset.faces.copy()),
+        # the tip pack of hands_mano_fit_f32: the rows of the five tip vertices, posedirs as (135, 15) [feature][3 tip + coordinate]
+        "tip_v_template": t(vt[tips]), "tip_shapedirs": t(sd[tips]), "tip_lbs_weights": t(_f32(asset.lbs_weights)[tips]),
+        "tip_posedirs": t(pd.reshape(135, 778, 3)[:, tips].reshape(135, 15)),
     }

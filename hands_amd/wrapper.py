@@ -48,6 +48,10 @@ class HandsWrapper(nn.Module):
         # a hands_amd.TemporalSmoother here makes forward(..., "test") smooth the predictions over consecutive calls (One-Euro
         # filter over the MANO parameters, re-posed) before the loss, the de-normalisation and the metrics; None: nothing changes
         self.smoother = None
+        # a hands_amd.FitConfig here makes process_data fit MANO to the annotated joints mano.j3d.full.{r,l} first
+        # (hands_amd.fit_targets): a keypoint-only batch, whose mano.pose / mano.beta are missing or dummies, then yields the
+        # full target dict and every metric family; None: nothing changes
+        self.fit_gt = None
 
     def inference_pose(self, inputs, meta_info):
         pred = self.model(inputs, meta_info)
@@ -72,6 +76,15 @@ class HandsWrapper(nn.Module):
         if dev.type != "cuda":
             raise RuntimeError("hands_amd.HandsWrapper runs on a HIP device only (no CPU fallback)")
         f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()
+        if self.fit_gt is not None:                 # as everything below: what arrives on the host is moved here
+            from .fitting import fit_targets
+            moved, flags = xdict(targets), dict(meta_info)
+            for h in "rl":
+                moved.overwrite(f"mano.j3d.full.{h}", f32(targets[f"mano.j3d.full.{h}"]))
+            for k in ("right_valid", "left_valid"):
+                if k in flags:
+                    flags[k] = f32(flags[k])
+            targets = fit_targets(moved, self.model, flags, self.fit_gt)
         K = f32(K)
         P = self.model.packed(dev)
         stream = torch.cuda.current_stream(dev).cuda_stream

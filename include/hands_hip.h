@@ -823,6 +823,46 @@ int hands_smooth_mano_f32(const hands_smooth_side* sides, int nsides, const long
                           const hands_smooth_cfg* cfg, hands_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * MANO fitting on device (csrc/fit.hip): a Levenberg-Marquardt fit of MANO to 21 3-D joints per hand -- the 16 rotations of the
+ * FULL pose (pose_mean added; hands_mano_heads_f32 takes it as axis-angle Log R_j - pose_mean_j), beta (10) and a translation (3).  DESIGN.md
+ * section 7 "MANO fitting" is the specification (residual, analytic Jacobian, damping, accept / reject); the reference has no
+ * counterpart.  One launch for both hands, grid (B, n_sides), one workgroup per hand, the hands independent: a hand's outputs
+ * do not depend on B, on its row, on n_sides or on the other rows.  No allocation, no host synchronisation, no atomics; exactly
+ * `iters` iterations whatever the data.  fp32 in, fp64 arithmetic, each output rounded once.
+ *
+ * Per side: joints (B,21,3) in metres, in this library's joint order (16 + the tips 744/320/443/554/671); weights (B,21) >= 0 or
+ * NULL (all 1) -- a joint of weight 0 is never read, its coordinates may be NaN; valid (B) or NULL (every row fitted);
+ * init_pose (B,16,3,3), init_beta (B,10), init_transl (B,3): all three (the initial state) or all NULL (the rest pose,
+ * rigidly aligned to the joints).  Outputs: pose (B,16,3,3), beta (B,10), transl (B,3), rmse (B) = sqrt(sum_k w_k |j_k + t -
+ * y_k|^2 / sum_k w_k) in metres, steps (B) int32 = accepted steps; they must not overlap the inputs or each other.
+ * A row is not fitted when valid == 0, fewer than four joints have weight > 0, a weighted joint or a given initial value is not
+ * finite: pose = (I, Exp(hands_mean_1..15)), beta = 0, transl = 0, rmse = NaN, steps = 0.  iters == 0 returns the initial state
+ * and its rmse.
+ * consts: pose_mean (48), J_template (16,3), J_shapedirs (48,10) as in hands_mano_consts, and the rows of the five tip vertices
+ * of v_template (5,3), shapedirs (5,3,10), lbs_weights (5,16) and their posedirs columns (135,15) [feature][3 tip + coordinate].
+ * HANDS_EINVAL (nothing launched): NULL sides / cfg, a NULL constant, joints or output of a side, one or two of init_* given,
+ * B <= 0, n_sides outside 1..2, iters < 0, lambda_beta / lambda_pose / mu0 negative or not finite.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct hands_mano_fit_consts {
+  const float *pose_mean, *J_template, *J_shapedirs;
+  const float *tip_v_template, *tip_shapedirs, *tip_lbs_weights, *tip_posedirs;
+} hands_mano_fit_consts;
+
+typedef struct hands_mano_fit_side {
+  hands_mano_fit_consts consts;
+  const float *joints, *weights, *valid, *init_pose, *init_beta, *init_transl;
+  float *pose, *beta, *transl, *rmse;
+  int32_t* steps;
+} hands_mano_fit_side;
+
+typedef struct hands_fit_cfg { /* lambda_*: weights of the shape and pose priors; mu0: the first damping */
+  int iters;
+  double lambda_beta, lambda_pose, mu0;
+} hands_fit_cfg;
+
+int hands_mano_fit_f32(const hands_mano_fit_side* sides, int n_sides, const hands_fit_cfg* cfg, int B, hands_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The validation loss dict on device, forward only (csrc/loss.hip): compute_loss_light of
  * src/callbacks/loss/loss_arctic_sf.py:20-206 (vector_loss / joints_loss / grasp_loss / render_loss of
  * src/utils/loss_modules.py:97-152) with the weighting and the total of src/models/generic/wrapper.py:19-23,100-115.
