@@ -123,6 +123,20 @@ class FitCfg(C.Structure):
     _fields_ = [("iters", C.c_int), ("lambda_beta", C.c_double), ("lambda_pose", C.c_double), ("mu0", C.c_double)]
 
 
+class ManoFit2DSide(C.Structure):
+    """hands_mano_fit2d_side (include/hands_hip.h): one hand of a hands_mano_fit2d_f32 call; weights, valid and init_* may be NULL."""
+    _fields_ = [("consts", ManoFitConsts)] + [(n, C.c_void_p) for n in (
+        "kp2d", "weights", "valid", "init_pose", "init_beta", "init_transl", "pose", "beta", "transl", "rmse", "steps", "start",
+        "j3d", "j2d")]
+
+
+class Fit2DCfg(C.Structure):
+    """hands_fit2d_cfg (include/hands_hip.h)."""
+    _fields_ = [("iters_rigid", C.c_int), ("iters", C.c_int), ("lambda_beta", C.c_double), ("lambda_pose", C.c_double),
+                ("mu0", C.c_double), ("robust_sigma", C.c_double), ("z_min", C.c_double), ("fit_shape", C.c_int),
+                ("prior_to_init", C.c_int)]
+
+
 class LossIn(C.Structure):
     """hands_loss_in (include/hands_hip.h): the first LOSS_N_MANDATORY pointers are mandatory, the rest come in groups."""
     _fields_ = [(n, C.c_void_p) for n in (
@@ -238,6 +252,7 @@ SIGNATURES = {
     "hands_eval_accel_metrics_f32": [C.POINTER(MeshEvalIn), _P, C.POINTER(AccelEvalOut), _I, _I, _F, _P],
     "hands_smooth_mano_f32": [C.POINTER(SmoothSide), _I, _P, _I, _I, _F, C.POINTER(SmoothCfg), _P],
     "hands_mano_fit_f32": [C.POINTER(ManoFitSide), _I, C.POINTER(FitCfg), _I, _P],
+    "hands_mano_fit2d_f32": [C.POINTER(ManoFit2DSide), _I, _P, C.POINTER(Fit2DCfg), _I, _P],
     "hands_loss_light_f32": [C.POINTER(LossIn), _I, _I, _I, _P, _P, _P, _P, _P],
     "hands_mano_pose_aa_f32": [C.POINTER(ManoConsts), _P, _P, _I, _P, _I, _P, _P, _I, _P],
     "hands_gt_targets_f32": [_P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _P],

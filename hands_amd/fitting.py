@@ -7,6 +7,11 @@ The reference has no fitter: DESIGN.md section 7 "MANO fitting" is the specifica
 The fit reproduces the JOINTS.  It does not recover a unique mesh: with joints alone, the twist of a finger segment about its
 own bone is observed only through the tips and the pose prior.  One launch fits both hands of a batch, one workgroup a hand;
 nothing here synchronises with the host.
+
+The ``*_2d`` functions fit the same unknowns to 21 2-D keypoints in pixels under the perspective projection of the intrinsics
+(hands_mano_fit2d_f32; DESIGN.md section 7 "MANO fitting to 2-D keypoints", tests/fit2d_ref.py): for 2-D-only annotations
+(``fit_targets_2d``, ``HandsWrapper.fit_gt_2d``) and for moving a prediction onto detected keypoints (``refine_predictions``).
+That fit reproduces the KEYPOINTS.  It does not recover depth, scale or a unique 3-D hand from one view.
 """
 from __future__ import annotations
 
@@ -16,7 +21,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from ._lib import FitCfg, ManoFitConsts, ManoFitSide, check, ptr
+from ._lib import Fit2DCfg, FitCfg, ManoFit2DSide, ManoFitConsts, ManoFitSide, check, ptr
 from .packing import pack_mano
 from .xdict import xdict
 
@@ -157,4 +162,209 @@ def fit_targets(targets, model, meta_info=None, config=None) -> xdict:
         out.overwrite(f"mano.beta.{h}", f["beta"])
         out.overwrite(f"mano.fit.rmse.{h}", f["rmse"])
         out.overwrite(f"mano.fit.transl.{h}", f["transl"])
+    return out
+
+
+# ---- fitting to 2-D keypoints ------------------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class Fit2DConfig:
+    """``iters_rigid`` iterations that free only the global rotation and the translation, then ``iters`` that free everything
+    (all but the shape with ``fit_shape=False``) -- exactly that many, no data-dependent exit; the weights ``lambda_beta`` and
+    ``lambda_pose`` of the priors; the first damping ``mu0`` (it restarts with the second stage); ``robust_sigma`` > 0 in pixels
+    switches the Geman-McClure kernel on; a state with a weighted joint at Z <= ``z_min`` metres is never accepted;
+    ``prior_to_init``: with a caller's initial state, both priors pull towards that state instead of the mean pose and beta = 0.
+
+    The defaults are UNTUNED starting values.  On the 16 cases of the tests (seeds 0..15 of ``fit2d_ref.family_case``: the
+    synthetic right asset's own joints projected with f = 1000 px, c = 112 px and rounded to fp32) the fp64 restatement reaches a
+    reprojection rmse of 1.2e-3 to 2.0 px, median 7.2e-3 px; 3 of the 16 stay above 1 px."""
+    iters_rigid: int = 10
+    iters: int = 30
+    lambda_beta: float = 1e-2
+    lambda_pose: float = 1e-2
+    mu0: float = 1e-3
+    robust_sigma: float = 0.0
+    z_min: float = 0.05
+    fit_shape: bool = True
+    prior_to_init: bool = False
+
+    def c_struct(self) -> Fit2DCfg:
+        for name in ("iters_rigid", "iters"):
+            v = getattr(self, name)
+            if int(v) != v or v < 0:
+                raise ValueError(f"hands_amd: {name} is a non-negative integer, got {v!r}")
+        for name in ("lambda_beta", "lambda_pose", "mu0", "robust_sigma"):
+            v = float(getattr(self, name))
+            if not (v >= 0.0 and v != float("inf")):
+                raise ValueError(f"hands_amd: {name} is finite and not negative, got {v!r}")
+        z = float(self.z_min)
+        if not (z > 0.0 and z != float("inf")):
+            raise ValueError(f"hands_amd: z_min is finite and positive, got {z!r}")
+        return Fit2DCfg(int(self.iters_rigid), int(self.iters), float(self.lambda_beta), float(self.lambda_pose), float(self.mu0),
+                        float(self.robust_sigma), z, int(bool(self.fit_shape)), int(bool(self.prior_to_init)))
+
+
+_INIT_SHAPES = (("pose", lambda B: (B, 16, 3, 3)), ("beta", lambda B: (B, 10)), ("transl", lambda B: (B, 3)))
+
+
+def _launch2d(packs, kp2d, K, weights, valids, inits, config, dev):
+    """One hands_mano_fit2d_f32 launch over len(packs) sides of B rows; -> per side (pose, beta, transl, rmse, steps, start,
+    j3d, j2d)."""
+    n, B = len(packs), kp2d[0].shape[0]
+    K = _opt(K, (B, 3, 3), dev, "intrinsics")
+    sides, outs, keep = (ManoFit2DSide * n)(), [], [K]
+    for i in range(n):
+        y = _opt(kp2d[i], (B, 21, 2), dev, "kp2d")
+        w, v = _opt(weights[i], (B, 21), dev, "weights"), _opt(valids[i], (B,), dev, "valid")
+        init = (None, None, None)
+        if inits[i] is not None:
+            init = tuple(_opt(a, s(B), dev, "init " + k) for a, (k, s) in zip(inits[i], _INIT_SHAPES))
+            if len(init) != 3 or any(a is None for a in init):
+                raise ValueError("hands_amd: init is (pose (B,16,3,3), beta (B,10), transl (B,3)), all three")
+        o = (torch.empty(B, 16, 3, 3, device=dev), torch.empty(B, 10, device=dev), torch.empty(B, 3, device=dev),
+             torch.empty(B, device=dev), torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+             torch.empty(B, 21, 3, device=dev), torch.empty(B, 21, 2, device=dev))
+        consts = ManoFitConsts(*[ptr(packs[i][k]) for k in _CONST_KEYS])
+        sides[i] = ManoFit2DSide(consts, ptr(y), ptr(w), ptr(v), ptr(init[0]), ptr(init[1]), ptr(init[2]), *[ptr(t) for t in o])
+        outs.append(o)
+        keep.append((y, w, v, init))           # converted copies stay alive until the launch is queued
+    cfg = (config or Fit2DConfig()).c_struct()
+    check(_lib.lib().hands_mano_fit2d_f32(sides, n, ptr(K), C.byref(cfg), B, torch.cuda.current_stream(dev).cuda_stream),
+          "hands_mano_fit2d_f32")
+    return outs
+
+
+def _result2d(pack, out):
+    """pose, beta, transl, rmse, steps, start, j3d, j2d and pose_aa (B,48), in that order."""
+    r = _result(pack, out[:5])
+    aa = r.pop("pose_aa")
+    r.update(start=out[5], j3d=out[6], j2d=out[7], pose_aa=aa)
+    return r
+
+
+def fit_mano_2d(kp2d, intrinsics, model_or_layer, side="r", weights=None, valid=None, init=None, config=None) -> xdict:
+    """Fit ONE hand of a batch to 2-D keypoints: ``kp2d`` (B,21,2) in PIXELS of the image ``intrinsics`` (B,3,3) belongs to (rows 0
+    and 1 are read), in this package's joint order, on the device, as every other tensor argument has to be (RuntimeError
+    otherwise).  ``weights`` (B,21) >= 0 (default 1; a keypoint of weight 0 is never read and may be NaN), ``valid`` (B),
+    ``init`` (pose (B,16,3,3), beta (B,10), transl (B,3)) instead of the state generated from the keypoints (the rest hand under
+    the best of the 24 axis-aligned rotations, placed by weak perspective), ``config`` a :class:`Fit2DConfig` (untuned defaults).
+
+    Returns an xdict: ``pose``, ``beta``, ``transl``, ``rmse`` (B) in pixels without the robust kernel and the priors, ``steps``
+    (B) int32, ``start`` (B) int32 -- the index of the generated start, -1 with ``init`` --, ``j3d`` (B,21,3) = joints + transl
+    in camera space, ``j2d`` (B,21,2) their projection in pixels, and ``pose_aa`` (B,48) as :func:`fit_mano` returns it.
+    The fit reproduces the KEYPOINTS: one view fixes neither depth nor scale nor a unique 3-D hand, and ``j3d`` may differ from
+    the true joints by centimetres at a sub-pixel ``rmse``.  A row that is not fitted (``valid`` 0, fewer than four weighted
+    keypoints, a non-finite weighted keypoint, intrinsic or initial value, K00 <= 0 or K11 <= 0, an initial state with a
+    weighted joint at Z <= z_min, no start candidate) has the mean pose, zeros, ``rmse`` NaN, 0 steps, ``start`` -1 and NaN in
+    ``j3d`` and ``j2d``."""
+    dev = _device_of(kp2d, "fit_mano_2d")
+    pack = _mano_pack(model_or_layer, side, dev)
+    return _result2d(pack, _launch2d([pack], [kp2d], intrinsics, [weights], [valid], [init], config, dev)[0])
+
+
+def fit_mano_hands_2d(kp2d_r, kp2d_l, intrinsics, model, weights_r=None, weights_l=None, valid_r=None, valid_l=None, init_r=None,
+                      init_l=None, config=None):
+    """Both hands of a batch in ONE launch, sharing ``intrinsics``: -> (right, left), each what :func:`fit_mano_2d` returns."""
+    dev = _device_of(kp2d_r, "fit_mano_hands_2d")
+    packs = [_mano_pack(model, "r", dev), _mano_pack(model, "l", dev)]
+    outs = _launch2d(packs, [kp2d_r, kp2d_l], intrinsics, [weights_r, weights_l], [valid_r, valid_l], [init_r, init_l], config, dev)
+    return _result2d(packs[0], outs[0]), _result2d(packs[1], outs[1])
+
+
+def _unnormalize(t, img_res):
+    """hands_unnormalize_kp2d_f32: 0.5 * img_res * (x + 1), the inverse of normalize_kp2d."""
+    t = t.to(dtype=torch.float32).contiguous()
+    out = torch.empty_like(t)
+    check(_lib.lib().hands_unnormalize_kp2d_f32(ptr(t), ptr(out), t.numel(), float(img_res),
+                                                torch.cuda.current_stream(t.device).cuda_stream), "unnormalize_kp2d")
+    return out
+
+
+def fit_targets_2d(targets, model, meta_info, weights_r=None, weights_l=None, config=None) -> xdict:
+    """Ground-truth MANO parameters for a 2-D-only batch: fits both hands to ``targets["mano.j2d.norm.{r,l}"]`` (un-normalised
+    with the model's ``img_res``) under ``meta_info["intrinsics"]`` in one launch and returns a NEW xdict with the entries of
+    ``targets`` in which ``mano.pose.{r,l}`` (B,48), ``mano.beta.{r,l}`` (B,10) and ``mano.j3d.full.{r,l}`` (B,21,3; the fit's
+    ``j3d``) are the fit, and ``mano.fit.rmse_px.{r,l}`` (B) and ``mano.fit.transl.{r,l}`` (B,3) are added; ``targets`` itself
+    is left as it was.  ``meta_info["right_valid"]`` / ``["left_valid"]``, where present, say which rows are fitted.  The 3-D
+    entries reproduce the keypoints, not the depth or scale of the true hand."""
+    dev = _device_of(targets["mano.j2d.norm.r"], "fit_targets_2d")
+    flag = lambda k: meta_info[k] if k in meta_info else None
+    res = float(getattr(model, "img_res", 224))
+    fits = fit_mano_hands_2d(_unnormalize(targets["mano.j2d.norm.r"], res), _unnormalize(targets["mano.j2d.norm.l"], res),
+                             meta_info["intrinsics"], model, weights_r=weights_r, weights_l=weights_l,
+                             valid_r=flag("right_valid"), valid_l=flag("left_valid"), config=config)
+    out = xdict(targets)
+    for h, f in zip("rl", fits):
+        out.overwrite(f"mano.pose.{h}", f["pose_aa"])
+        out.overwrite(f"mano.beta.{h}", f["beta"])
+        out.overwrite(f"mano.j3d.full.{h}", f["j3d"])
+        out.overwrite(f"mano.fit.rmse_px.{h}", f["rmse"])
+        out.overwrite(f"mano.fit.transl.{h}", f["transl"])
+    return out
+
+
+_HEAD_KEYS = ("cam_t.wp", "cam_t", "joints3d", "vertices", "j3d.cam", "v3d.cam", "j2d.norm", "beta", "pose")
+MIN_WP_SCALE = 0.1           # the clamp of the MANO head's weak-perspective scale (hands_mano_heads_f32's min_s)
+
+
+def _aa_to_matrix(aa):
+    """(B,48) axis-angle -> (B,16,3,3) through hands_axis_angle_to_matrix_f32."""
+    aa = aa.contiguous()
+    rot = torch.empty(aa.shape[0], 16, 3, 3, device=aa.device)
+    check(_lib.lib().hands_axis_angle_to_matrix_f32(ptr(aa), ptr(rot), aa.shape[0] * 16,
+                                                    torch.cuda.current_stream(aa.device).cuda_stream), "axis_angle_to_matrix")
+    return rot
+
+
+def refine_predictions(pred, kp2d_r, kp2d_l, model, meta_info, weights_r=None, weights_l=None, valid_r=None, valid_l=None,
+                       config=None) -> xdict:
+    """Test-time refinement: move a model's prediction so that it re-projects onto detected keypoints ``kp2d_{r,l}`` (B,21,2) in
+    pixels of the image ``meta_info["intrinsics"]`` belongs to.  The fit starts from the prediction -- the full pose
+    Exp(Log(``mano.pose``_j) + hands_mean_j), ``mano.beta`` and ``mano.cam_t`` as the translation --; the default ``config`` is
+    ``Fit2DConfig(iters_rigid=0, prior_to_init=True)``: no rigid stage, the priors pull towards the prediction.  The nine MANO-head
+    keys per hand are then recomputed by one ``hands_mano_heads_f32`` launch (as ``smooth_predictions`` does) from the rotations
+    before the mean, the fitted beta and the weak-perspective camera that gives the fitted translation back; every other key of
+    ``pred`` is handed through, in the order of ``pred``.  Added: ``refined.{r,l}`` (B) bool, the rows that moved.
+
+    A row that is not fitted keeps the prediction's tensors bit for bit.  So does a row whose fitted depth cannot be represented:
+    the head clamps the weak-perspective scale at 0.1, so a depth beyond 2 f / (0.1 img_res) -- 89 m at f = 1000, img_res = 224
+    -- is not refined.  The translation goes through the head's fp32 camera conversion, so the refined ``mano.cam_t`` is the
+    fitted one to fp32 rounding of its depth."""
+    from .mano_head import run_mano_heads
+    dev = _device_of(pred["mano.pose.r"], "refine_predictions")
+    L, stream = _lib.lib(), torch.cuda.current_stream(dev).cuda_stream
+    P = model.packed(dev)
+    f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()
+    K = f32(meta_info["intrinsics"])
+    B = pred["mano.pose.r"].shape[0]
+    inits = []
+    for h in "rl":
+        pose = f32(pred[f"mano.pose.{h}"])
+        aa = torch.empty(B, 48, device=dev)
+        check(L.hands_matrix_to_axis_angle_f32(ptr(pose), ptr(aa), B * 16, stream), "matrix_to_axis_angle")
+        inits.append((_aa_to_matrix(aa + P[f"mano_{h}"]["pose_mean"]), f32(pred[f"mano.beta.{h}"]), f32(pred[f"mano.cam_t.{h}"])))
+    config = config or Fit2DConfig(iters_rigid=0, prior_to_init=True)
+    fits = fit_mano_hands_2d(kp2d_r, kp2d_l, K, model, weights_r, weights_l, valid_r, valid_l, inits[0], inits[1], config)
+    res = float(getattr(model, "img_res", 224))
+    focal = 0.5 * (K[:, 0, 0] + K[:, 1, 1])
+    rot, shape, cam = torch.empty(2 * B, 16, 3, 3, device=dev), torch.empty(2 * B, 10, device=dev), torch.empty(2 * B, 3, device=dev)
+    moved = []
+    for i, (h, f) in enumerate(zip("rl", fits)):
+        t = f["transl"]
+        s = (2.0 * focal / t[:, 2] - 1e-9) / res       # the inverse of weak_perspective_to_perspective: t_z = 2 f / (res s + 1e-9)
+        ok = torch.isfinite(f["rmse"]) & (s >= MIN_WP_SCALE)
+        wp = torch.stack([s, t[:, 0], t[:, 1]], 1)
+        sl = slice(i * B, (i + 1) * B)
+        rot[sl] = torch.where(ok[:, None, None, None], _aa_to_matrix(f["pose_aa"]), f32(pred[f"mano.pose.{h}"]))
+        shape[sl] = torch.where(ok[:, None], f["beta"], f32(pred[f"mano.beta.{h}"]))
+        cam[sl] = torch.where(ok[:, None], wp, f32(pred[f"mano.cam_t.wp.{h}"]))
+        moved.append(ok)
+    new = run_mano_heads(L, P["mano_r"], P["mano_l"], rot, shape, cam, cam, K, res, B, stream, None)
+    out = xdict()
+    for k, v in pred.items():
+        parts = k.rsplit(".", 1)
+        if len(parts) == 2 and parts[1] in ("r", "l") and parts[0].startswith("mano.") and parts[0][5:] in _HEAD_KEYS:
+            ok = moved["rl".index(parts[1])]
+            v = torch.where(ok.view((-1,) + (1,) * (v.dim() - 1)), new[k].to(v.dtype), v)
+        out[k] = v
+    out["refined.r"], out["refined.l"] = moved
     return out

@@ -52,6 +52,10 @@ class HandsWrapper(nn.Module):
         # (hands_amd.fit_targets): a keypoint-only batch, whose mano.pose / mano.beta are missing or dummies, then yields the
         # full target dict and every metric family; None: nothing changes
         self.fit_gt = None
+        # a hands_amd.Fit2DConfig here makes process_data fit MANO to the annotated 2-D keypoints mano.j2d.norm.{r,l} first
+        # (hands_amd.fit_targets_2d): a 2-D-only batch, whose mano.j3d.full are zeros, then yields a full target dict that
+        # re-projects onto the annotation (depth and scale are not recovered); setting both fits raises; None: nothing changes
+        self.fit_gt_2d = None
 
     def inference_pose(self, inputs, meta_info):
         pred = self.model(inputs, meta_info)
@@ -70,12 +74,25 @@ class HandsWrapper(nn.Module):
         """Adds mano.{joints3d,vertices,cam_t,cam_t.wp,v3d.cam,j3d.cam}.{r,l} to ``targets`` from the GT
         MANO parameters (axis-angle pose (B,48), betas (B,10)) and the annotated camera-space joints
         ``mano.j3d.full.{r,l}``; MANO runs on the same LBS kernels as the prediction path."""
+        if self.fit_gt is not None and self.fit_gt_2d is not None:
+            raise ValueError("hands_amd.HandsWrapper: fit_gt and fit_gt_2d are both set; a batch is fitted to 3-D joints or to "
+                             "2-D keypoints, not both")
         L = _lib.lib()
         K = meta_info["intrinsics"]
         dev = K.device
         if dev.type != "cuda":
             raise RuntimeError("hands_amd.HandsWrapper runs on a HIP device only (no CPU fallback)")
         f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()
+        if self.fit_gt_2d is not None:
+            from .fitting import fit_targets_2d
+            moved, flags = xdict(targets), dict(meta_info)
+            for h in "rl":
+                moved.overwrite(f"mano.j2d.norm.{h}", f32(targets[f"mano.j2d.norm.{h}"]))
+            flags["intrinsics"] = f32(K)
+            for k in ("right_valid", "left_valid"):
+                if k in flags:
+                    flags[k] = f32(flags[k])
+            targets = fit_targets_2d(moved, self.model, flags, config=self.fit_gt_2d)
         if self.fit_gt is not None:                 # as everything below: what arrives on the host is moved here
             from .fitting import fit_targets
             moved, flags = xdict(targets), dict(meta_info)

@@ -863,6 +863,46 @@ typedef struct hands_fit_cfg { /* lambda_*: weights of the shape and pose priors
 int hands_mano_fit_f32(const hands_mano_fit_side* sides, int n_sides, const hands_fit_cfg* cfg, int B, hands_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * MANO fitting to 2-D keypoints (csrc/fit.hip, beside the 3-D fit and on its device routines): the same 61 unknowns fitted to 21
+ * keypoints in PIXELS under the perspective projection of K.  DESIGN.md section 7 "MANO fitting to 2-D keypoints" is the
+ * specification, tests/fit2d_ref.py its fp64 restatement.  Launch and guarantees as hands_mano_fit_f32: grid (B, n_sides), one
+ * four-wave workgroup per hand, fp32 in, fp64 arithmetic, one rounding per output, no atomics, no allocation, no host
+ * synchronisation (the call can be captured); a hand's outputs do not depend on B, its row, n_sides or its neighbours; exactly
+ * iters_rigid + iters iterations whatever the data.  The fit reproduces the KEYPOINTS; depth, scale and the 3-D hand are not
+ * recovered uniquely from one view.
+ *
+ * Per side the fields of hands_mano_fit_side with kp2d (B,21,2) in place of joints, and three more outputs: start (B) int32, the
+ * index 0..23 of the signed permutation the generated initial state took (-1 with a caller's state or a row not fitted), j3d
+ * (B,21,3) = joints + transl in camera space and j2d (B,21,2) = their projection in pixels, both for all 21 joints.  K (B,3,3),
+ * shared by the sides; only rows 0 and 1 are read.  rmse = sqrt(sum_k w_k |pi(X_k) - y_k|^2 / sum_k w_k) in pixels, without the
+ * robust kernel and the priors.
+ * cfg: iters_rigid iterations that free only the global rotation and the translation, then iters that free everything (or all
+ * but beta with fit_shape == 0); robust_sigma > 0 switches the Geman-McClure kernel on (pixels); a state in which a weighted
+ * joint has Z <= z_min costs +inf; prior_to_init != 0 with a caller's state makes that state the reference of both priors.
+ * A row is not fitted when valid == 0, fewer than four keypoints have weight > 0, a weighted keypoint, an entry of K rows 0-1 or a
+ * given initial value is not finite, K00 <= 0 or K11 <= 0, the initial state trips the depth guard, or no start candidate
+ * qualifies: the outputs of an unfitted row of hands_mano_fit_f32, start = -1, j3d and j2d NaN.
+ * HANDS_EINVAL (nothing launched): the cases of hands_mano_fit_f32, a NULL K, start, j3d or j2d, iters_rigid < 0, robust_sigma
+ * negative or not finite, z_min not finite or <= 0.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct hands_mano_fit2d_side {
+  hands_mano_fit_consts consts;
+  const float *kp2d, *weights, *valid, *init_pose, *init_beta, *init_transl;
+  float *pose, *beta, *transl, *rmse;
+  int32_t *steps, *start;
+  float *j3d, *j2d;
+} hands_mano_fit2d_side;
+
+typedef struct hands_fit2d_cfg {
+  int iters_rigid, iters;
+  double lambda_beta, lambda_pose, mu0, robust_sigma, z_min;
+  int fit_shape, prior_to_init;
+} hands_fit2d_cfg;
+
+int hands_mano_fit2d_f32(const hands_mano_fit2d_side* sides, int n_sides, const float* K, const hands_fit2d_cfg* cfg, int B,
+                         hands_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The validation loss dict on device, forward only (csrc/loss.hip): compute_loss_light of
  * src/callbacks/loss/loss_arctic_sf.py:20-206 (vector_loss / joints_loss / grasp_loss / render_loss of
  * src/utils/loss_modules.py:97-152) with the weighting and the total of src/models/generic/wrapper.py:19-23,100-115.
