@@ -57,8 +57,8 @@ def dproject(K, X):
                      [K[1, 0] / z, K[1, 1] / z, -(K[1, 0] * x + K[1, 1] * y) / (z * z)]])
 
 
-def start_state(C, y, w, K):
-    """The initial state from 2-D alone -> (c, R (16,3,3), beta, t) or None when no candidate qualifies."""
+def start_scores(C, y, w, K):
+    """(eps, c, s, ab) of every start candidate that qualifies, in the order of START, and the rest hand's J_0."""
     R, beta = F.rest_pose(C), np.zeros(10)
     E = F.evaluate(C, R, beta)
     J0 = E["J"][0]
@@ -69,7 +69,7 @@ def start_state(C, y, w, K):
     d = y[sel] - K[:2, 2]
     n = np.stack([(K[1, 1] * d[:, 0] - K[0, 1] * d[:, 1]) / det, (K[0, 0] * d[:, 1] - K[1, 0] * d[:, 0]) / det], 1)
     nb = (ws[:, None] * n).sum(0) / ws.sum()
-    best = None
+    out = []
     for c, G in enumerate(START):
         a = (x[sel] @ G.T)[:, :2]
         ab = (ws[:, None] * a).sum(0) / ws.sum()
@@ -82,10 +82,20 @@ def start_state(C, y, w, K):
         eps = float((ws * ((s * (a - ab) - (n - nb)) ** 2).sum(1)).sum())
         if not eps < math.inf:                            # a singular K[:2,:2]: no candidate qualifies
             continue
-        if best is None or eps < best[0]:
-            best = (eps, c, s, ab)
+        out.append((eps, c, s, ab))
+    return out, nb, J0
+
+
+def start_state(C, y, w, K):
+    """The initial state from 2-D alone -> (c, R (16,3,3), beta, t) or None when no candidate qualifies."""
+    scores, nb, J0 = start_scores(C, y, w, K)
+    best = None
+    for cand in scores:                                   # the smallest, ties to the lowest index
+        if best is None or cand[0] < best[0]:
+            best = cand
     if best is None:
         return None
+    R, beta = F.rest_pose(C), np.zeros(10)
     _, c, s, ab = best
     tau = (nb - s * ab) / s
     R[0] = START[c]
@@ -175,6 +185,7 @@ def fit(C, y, K, w=None, valid=None, init=None, cfg=None, noise=0.0, seed=0):
     if not (K[0, 0] > 0 and K[1, 1] > 0):
         return unfitted(C)
     y = np.where(sel[:, None], y32.astype(np.float64), 0.0)                    # unweighted keypoints are never read
+    w = np.where(sel, w, 0.0)                                                  # nor is a weight that is negative or no number
     prior = (np.zeros(10), C.M)
     if init is not None:
         R, beta, t = (np.asarray(a, np.float32).astype(np.float64) for a in init)

@@ -207,6 +207,7 @@ def fit(C, y, w=None, valid=None, init=None, cfg=None, noise=0.0, seed=0):
     if (valid is not None and valid == 0) or sel.sum() < 4 or not np.isfinite(y32[sel]).all():
         return unfitted(C)
     y = np.where(sel[:, None], y32.astype(np.float64), 0.0)                    # unweighted joints are never read
+    w = np.where(sel, w, 0.0)                                                  # nor is a weight that is negative or no number
     if init is not None:
         R, beta, t = (np.asarray(a, np.float32).astype(np.float64) for a in init)
         if not (np.isfinite(R).all() and np.isfinite(beta).all() and np.isfinite(t).all()):
