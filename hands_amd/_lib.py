@@ -137,6 +137,19 @@ class Fit2DCfg(C.Structure):
                 ("prior_to_init", C.c_int)]
 
 
+class ManoFitVertsConsts(C.Structure):
+    """hands_mano_fit_verts_consts (include/hands_hip.h): the three joint constants and the full vertex constants."""
+    _fields_ = [(n, C.c_void_p) for n in ("pose_mean", "J_template", "J_shapedirs", "v_template", "shapedirs", "lbs_weights",
+                                          "posedirs_vm")]
+
+
+class ManoFitVertsSide(C.Structure):
+    """hands_mano_fit_verts_side (include/hands_hip.h): one hand of a hands_mano_fit_verts_f32 call; weights, valid and init_* may
+    be NULL."""
+    _fields_ = [("consts", ManoFitVertsConsts)] + [(n, C.c_void_p) for n in (
+        "verts", "weights", "valid", "init_pose", "init_beta", "init_transl", "pose", "beta", "transl", "rmse", "steps", "j3d")]
+
+
 class LossIn(C.Structure):
     """hands_loss_in (include/hands_hip.h): the first LOSS_N_MANDATORY pointers are mandatory, the rest come in groups."""
     _fields_ = [(n, C.c_void_p) for n in (
@@ -253,6 +266,7 @@ SIGNATURES = {
     "hands_smooth_mano_f32": [C.POINTER(SmoothSide), _I, _P, _I, _I, _F, C.POINTER(SmoothCfg), _P],
     "hands_mano_fit_f32": [C.POINTER(ManoFitSide), _I, C.POINTER(FitCfg), _I, _P],
     "hands_mano_fit2d_f32": [C.POINTER(ManoFit2DSide), _I, _P, C.POINTER(Fit2DCfg), _I, _P],
+    "hands_mano_fit_verts_f32": [C.POINTER(ManoFitVertsSide), _I, C.POINTER(FitCfg), _I, _P],
     "hands_loss_light_f32": [C.POINTER(LossIn), _I, _I, _I, _P, _P, _P, _P, _P],
     "hands_mano_pose_aa_f32": [C.POINTER(ManoConsts), _P, _P, _I, _P, _I, _P, _P, _I, _P],
     "hands_gt_targets_f32": [_P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _P],

@@ -12,6 +12,13 @@ The ``*_2d`` functions fit the same unknowns to 21 2-D keypoints in pixels under
 (hands_mano_fit2d_f32; DESIGN.md section 7 "MANO fitting to 2-D keypoints", tests/fit2d_ref.py): for 2-D-only annotations
 (``fit_targets_2d``, ``HandsWrapper.fit_gt_2d``) and for moving a prediction onto detected keypoints (``refine_predictions``).
 That fit reproduces the KEYPOINTS.  It does not recover depth, scale or a unique 3-D hand from one view.
+
+The ``*_verts`` functions fit the same unknowns to the 778 vertices of a mesh in MANO topology (hands_mano_fit_verts_f32,
+csrc/fit_verts.hip; DESIGN.md section 7 "MANO fitting to 778 vertices", tests/fit_verts_ref.py): for mesh-only annotations
+(``fit_targets_verts``, ``HandsWrapper.fit_gt_verts``) and for turning any MANO-topology mesh into ``mano.pose`` /
+``mano.beta``.  That fit reproduces the VERTICES: where the mesh is a MANO mesh it recovers pose and shape.  It does no
+correspondence-free registration (no ICP to a surface or a point cloud: vertex n of the target is vertex n of the model) and
+fits no scale.
 """
 from __future__ import annotations
 
@@ -21,7 +28,8 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from ._lib import Fit2DCfg, FitCfg, ManoFit2DSide, ManoFitConsts, ManoFitSide, check, ptr
+from ._lib import (Fit2DCfg, FitCfg, ManoFit2DSide, ManoFitConsts, ManoFitSide, ManoFitVertsConsts, ManoFitVertsSide, check,
+                   ptr)
 from .packing import pack_mano
 from .xdict import xdict
 
@@ -36,7 +44,15 @@ class FitConfig:
     The defaults (30, 1e-6, 1e-6, 1e-3) are starting values and NOT tuned on data.  On the 16 cases of the tests
     (``fit_ref.FULL_SEEDS``: joints the synthetic right asset generates itself -- global rotation 2 randn, fingers hands_mean +
     0.5 randn, beta = randn, rounded to fp32) the fp64 restatement reaches an rmse of 9.4e-5 to 4.2e-4 m, median 1.6e-4 m -- the
-    priors set that floor."""
+    priors set that floor.
+
+    The fit to 778 vertices (``fit_mano_verts``) takes the same four numbers.  There the restatement
+    (``fit_verts_ref.family_case``, both synthetic assets, 16 fully weighted cases) takes 5 or 6 real steps, reaches an rmse of
+    at most 9.5e-7 m and recovers the rotations to 1.8e-5 rad, beta to 8.6e-5 and the translation to 4.6e-7 m: on a fully
+    weighted, noise-free mesh the iterations after about the sixth change nothing and cost time.  Sparse targets (20 of the
+    778 vertices weighted) are what need the thirty: they take 15 to 30 iterations with rejections on the way.  Once the cost
+    has stalled, an accept / reject decision is a tie at rounding level (|c' - c| <= 4e-16 c, often exactly 0), so ``steps``
+    past convergence carries no information; there is no stall rule and no tolerance in the accept test."""
     iters: int = 30
     lambda_beta: float = 1e-6
     lambda_pose: float = 1e-6
@@ -367,4 +383,92 @@ def refine_predictions(pred, kp2d_r, kp2d_l, model, meta_info, weights_r=None, w
             v = torch.where(ok.view((-1,) + (1,) * (v.dim() - 1)), new[k].to(v.dtype), v)
         out[k] = v
     out["refined.r"], out["refined.l"] = moved
+    return out
+
+
+# ---- fitting to 778 vertices -------------------------------------------------------------------------------------------------
+_VERTS_CONST_KEYS = ("pose_mean", "J_template", "J_shapedirs", "v_template", "shapedirs", "lbs_weights", "posedirs_vm")
+
+
+def _launch_verts(packs, verts, weights, valids, inits, config, dev):
+    """One hands_mano_fit_verts_f32 launch over len(packs) sides of B rows; -> per side (pose, beta, transl, rmse, steps, j3d)."""
+    n, B = len(packs), verts[0].shape[0]
+    sides, outs, keep = (ManoFitVertsSide * n)(), [], []
+    for i in range(n):
+        y = _opt(verts[i], (B, 778, 3), dev, "verts")
+        w, v = _opt(weights[i], (B, 778), dev, "weights"), _opt(valids[i], (B,), dev, "valid")
+        init = (None, None, None)
+        if inits[i] is not None:
+            init = tuple(_opt(a, s(B), dev, "init " + k) for a, (k, s) in zip(inits[i], _INIT_SHAPES))
+            if len(init) != 3 or any(a is None for a in init):
+                raise ValueError("hands_amd: init is (pose (B,16,3,3), beta (B,10), transl (B,3)), all three")
+        o = (torch.empty(B, 16, 3, 3, device=dev), torch.empty(B, 10, device=dev), torch.empty(B, 3, device=dev),
+             torch.empty(B, device=dev), torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, 21, 3, device=dev))
+        consts = ManoFitVertsConsts(*[ptr(packs[i][k]) for k in _VERTS_CONST_KEYS])
+        sides[i] = ManoFitVertsSide(consts, ptr(y), ptr(w), ptr(v), ptr(init[0]), ptr(init[1]), ptr(init[2]), *[ptr(t) for t in o])
+        outs.append(o)
+        keep.append((y, w, v, init))           # converted copies stay alive until the launch is queued
+    cfg = (config or FitConfig()).c_struct()
+    check(_lib.lib().hands_mano_fit_verts_f32(sides, n, C.byref(cfg), B, torch.cuda.current_stream(dev).cuda_stream),
+          "hands_mano_fit_verts_f32")
+    return outs
+
+
+def _result_verts(pack, out):
+    """pose, beta, transl, rmse, steps, j3d and pose_aa (B,48), in that order."""
+    r = _result(pack, out[:5])
+    aa = r.pop("pose_aa")
+    r.update(j3d=out[5], pose_aa=aa)
+    return r
+
+
+def fit_mano_verts(verts, model_or_layer, side="r", weights=None, valid=None, init=None, config=None) -> xdict:
+    """Fit ONE hand of a batch to the vertices of a mesh in MANO topology: ``verts`` (B,778,3) in metres, vertex n the model's
+    vertex n, on the device, as every other tensor argument has to be (RuntimeError otherwise).  ``weights`` (B,778) >= 0
+    (default 1; a vertex of weight 0 is never read and may be NaN: that is how a partial or occluded mesh is fitted), ``valid``
+    (B), ``init`` (pose (B,16,3,3), beta (B,10), transl (B,3)) instead of the rest hand aligned rigidly to the weighted vertices,
+    ``config`` a :class:`FitConfig` (untuned defaults; see there what the thirty iterations are for).
+
+    Returns an xdict: ``pose``, ``beta``, ``transl``, ``rmse`` (B) in metres without the priors, ``steps`` (B) int32 accepted
+    steps -- past convergence a decision is a tie at rounding level and ``steps`` carries no information --, ``j3d`` (B,21,3) =
+    the fitted joints + transl, and ``pose_aa`` (B,48) as :func:`fit_mano` returns it.  The fit reproduces the VERTICES and, where
+    the mesh is a MANO mesh, recovers pose and shape; it does not register a surface or a point cloud without correspondences
+    and fits no scale.  A row that is not fitted (``valid`` 0, fewer than four weighted vertices, a non-finite weighted vertex
+    or initial value) has the mean pose, zeros, ``rmse`` NaN, 0 steps and NaN in ``j3d``."""
+    (config or FitConfig()).c_struct()             # a bad configuration is refused before anything else is looked at
+    dev = _device_of(verts, "fit_mano_verts")
+    pack = _mano_pack(model_or_layer, side, dev)
+    return _result_verts(pack, _launch_verts([pack], [verts], [weights], [valid], [init], config, dev)[0])
+
+
+def fit_mano_hands_verts(verts_r, verts_l, model, weights_r=None, weights_l=None, valid_r=None, valid_l=None, init_r=None,
+                         init_l=None, config=None):
+    """Both hands of a batch in ONE launch: -> (right, left), each what :func:`fit_mano_verts` returns."""
+    (config or FitConfig()).c_struct()
+    dev = _device_of(verts_r, "fit_mano_hands_verts")
+    packs = [_mano_pack(model, "r", dev), _mano_pack(model, "l", dev)]
+    outs = _launch_verts(packs, [verts_r, verts_l], [weights_r, weights_l], [valid_r, valid_l], [init_r, init_l], config, dev)
+    return _result_verts(packs[0], outs[0]), _result_verts(packs[1], outs[1])
+
+
+def fit_targets_verts(targets, model, meta_info=None, config=None) -> xdict:
+    """Ground-truth MANO parameters for a mesh-only batch: fits both hands to ``targets["mano.v3d.full.{r,l}"]`` (B,778,3; camera
+    space, metres, on the device: the vertex counterpart of ``mano.j3d.full``) in one launch and returns a NEW xdict with the
+    entries of ``targets`` in which ``mano.pose.{r,l}`` (B,48) and ``mano.beta.{r,l}`` (B,10) are the fit, ``mano.fit.rmse.{r,l}``
+    (B) and ``mano.fit.transl.{r,l}`` (B,3) are added, and ``mano.j3d.full.{r,l}`` is the fit's ``j3d`` where ``targets`` has no
+    such key (a present one is left alone); ``targets`` itself is left as it was.  ``meta_info["right_valid"]`` /
+    ``["left_valid"]`` (B, on the device), where present, say which rows are fitted."""
+    (config or FitConfig()).c_struct()
+    dev = _device_of(targets["mano.v3d.full.r"], "fit_targets_verts")
+    flag = lambda k: meta_info[k] if meta_info is not None and k in meta_info else None
+    fits = fit_mano_hands_verts(targets["mano.v3d.full.r"], targets["mano.v3d.full.l"], model, valid_r=flag("right_valid"),
+                                valid_l=flag("left_valid"), config=config)
+    out = xdict(targets)
+    for h, f in zip("rl", fits):
+        out.overwrite(f"mano.pose.{h}", f["pose_aa"])
+        out.overwrite(f"mano.beta.{h}", f["beta"])
+        out.overwrite(f"mano.fit.rmse.{h}", f["rmse"])
+        out.overwrite(f"mano.fit.transl.{h}", f["transl"])
+        if f"mano.j3d.full.{h}" not in targets:
+            out.overwrite(f"mano.j3d.full.{h}", f["j3d"])
     return out

@@ -178,4 +178,8 @@ def pack_mano(asset: ManoAsset, device):
         # the tip pack of hands_mano_fit_f32: the rows of the five tip vertices, posedirs as (135, 15) [feature][3 tip + coordinate]
         "tip_v_template": t(vt[tips]), "tip_shapedirs": t(sd[tips]), "tip_lbs_weights": t(_f32(asset.lbs_weights)[tips]),
         "tip_posedirs": t(pd.reshape(135, 778, 3)[:, tips].reshape(135, 15)),
+        # what hands_mano_fit_verts_f32 reads beside them: the full v_template (778,3) and shapedirs (778,3,10), and posedirs with
+        # the vertex first, (778, 135, 3) [vertex][feature][coordinate], so that a vertex's 405 values are contiguous
+        "v_template": t(vt.reshape(778, 3)), "shapedirs": t(sd.reshape(778, 3, 10)),
+        "posedirs_vm": t(pd.reshape(135, 778, 3).transpose(1, 0, 2)),
     }

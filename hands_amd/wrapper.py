@@ -24,6 +24,11 @@ from .xdict import xdict
 
 
 class HandsWrapper(nn.Module):
+    # a hands_amd.FitConfig here makes process_data fit MANO to the annotated vertices mano.v3d.full.{r,l} (B,778,3) first
+    # (hands_amd.fit_targets_verts): a mesh-only batch then yields the full target dict, mano.j3d.full from the fit where the
+    # batch has none; more than one of the three fits set raises; None: nothing changes
+    fit_gt_verts = None
+
     def __init__(self, args=None, push_images_fn=None, model: HandsLight | None = None):
         super().__init__()
         args = args if args is not None else DEFAULT_ARGS
@@ -77,12 +82,24 @@ class HandsWrapper(nn.Module):
         if self.fit_gt is not None and self.fit_gt_2d is not None:
             raise ValueError("hands_amd.HandsWrapper: fit_gt and fit_gt_2d are both set; a batch is fitted to 3-D joints or to "
                              "2-D keypoints, not both")
+        if self.fit_gt_verts is not None and (self.fit_gt is not None or self.fit_gt_2d is not None):
+            raise ValueError("hands_amd.HandsWrapper: fit_gt_verts is set beside fit_gt or fit_gt_2d; a batch is fitted to 3-D "
+                             "joints, to 2-D keypoints or to vertices, to one of them")
         L = _lib.lib()
         K = meta_info["intrinsics"]
         dev = K.device
         if dev.type != "cuda":
             raise RuntimeError("hands_amd.HandsWrapper runs on a HIP device only (no CPU fallback)")
         f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()
+        if self.fit_gt_verts is not None:           # as everything below: what arrives on the host is moved here
+            from .fitting import fit_targets_verts
+            moved, flags = xdict(targets), dict(meta_info)
+            for h in "rl":
+                moved.overwrite(f"mano.v3d.full.{h}", f32(targets[f"mano.v3d.full.{h}"]))
+            for k in ("right_valid", "left_valid"):
+                if k in flags:
+                    flags[k] = f32(flags[k])
+            targets = fit_targets_verts(moved, self.model, flags, self.fit_gt_verts)
         if self.fit_gt_2d is not None:
             from .fitting import fit_targets_2d
             moved, flags = xdict(targets), dict(meta_info)

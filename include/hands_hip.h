@@ -903,6 +903,46 @@ int hands_mano_fit2d_f32(const hands_mano_fit2d_side* sides, int n_sides, const 
                          hands_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * MANO fitting to 778 vertices (csrc/fit_verts.hip, on the device routines of csrc/fit_device.h): the same 61 unknowns fitted to
+ * the 778 vertices of a mesh in MANO topology, in metres.  DESIGN.md section 7 "MANO fitting to 778 vertices" is the
+ * specification, tests/fit_verts_ref.py its fp64 restatement.  Launch and guarantees as hands_mano_fit_f32: grid (B, n_sides),
+ * one four-wave workgroup per hand, fp32 in, fp64 arithmetic, one rounding per output, no atomics, no allocation, no host
+ * synchronisation (the call can be captured); every sum has an order the code alone fixes: a hand's outputs do not depend on
+ * B, its row, n_sides or its neighbours and are the same bits from launch to launch; exactly iters iterations whatever the
+ * data.  The fit reproduces the VERTICES: where the mesh is a MANO mesh it recovers pose and shape; it does no
+ * correspondence-free registration (vertex n of the target is vertex n of the model) and fits no scale.
+ *
+ * Per side the fields of hands_mano_fit_side with verts (B,778,3) in place of joints and weights (B,778) >= 0 or NULL (all 1) -- a
+ * vertex of weight 0 (or of a weight that is negative or no number) is never read, its coordinates may be NaN: that is how a
+ * partial or occluded mesh is fitted --, and one more output: j3d (B,21,3) = the fitted joints (16 + the tips 744/320/443/554/671)
+ * + transl.  rmse = sqrt(sum_n w_n |v_n + t - y_n|^2 / sum_n w_n) in metres, priors left out.  The initial state without init_*
+ * is the rest hand under the weighted rigid alignment of its vertices onto verts.
+ * A row is not fitted when valid == 0, fewer than four vertices have weight > 0, a weighted vertex or a given initial value is
+ * not finite: the outputs of an unfitted row of hands_mano_fit_f32, j3d NaN.  iters == 0 returns the initial state, its rmse
+ * and its j3d.
+ * consts: pose_mean (48), J_template (16,3), J_shapedirs (48,10) as in hands_mano_fit_consts; v_template (778,3), shapedirs
+ * (778,3,10) and lbs_weights (778,16) as the asset has them; posedirs_vm (778,135,3): the asset's posedirs (135, 778*3) with the
+ * vertex first, posedirs_vm[(n * 135 + f) * 3 + c] = posedirs[f][3 n + c], so that a vertex's 405 values are contiguous.
+ * HANDS_EINVAL (nothing launched): the cases of hands_mano_fit_f32, a NULL among these constants, a NULL verts or j3d.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct hands_mano_fit_verts_consts {
+  const float *pose_mean, *J_template, *J_shapedirs;
+  const float *v_template, *shapedirs, *lbs_weights;
+  const float* posedirs_vm;
+} hands_mano_fit_verts_consts;
+
+typedef struct hands_mano_fit_verts_side {
+  hands_mano_fit_verts_consts consts;
+  const float *verts, *weights, *valid, *init_pose, *init_beta, *init_transl;
+  float *pose, *beta, *transl, *rmse;
+  int32_t* steps;
+  float* j3d;
+} hands_mano_fit_verts_side;
+
+int hands_mano_fit_verts_f32(const hands_mano_fit_verts_side* sides, int n_sides, const hands_fit_cfg* cfg, int B,
+                             hands_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The validation loss dict on device, forward only (csrc/loss.hip): compute_loss_light of
  * src/callbacks/loss/loss_arctic_sf.py:20-206 (vector_loss / joints_loss / grasp_loss / render_loss of
  * src/utils/loss_modules.py:97-152) with the weighting and the total of src/models/generic/wrapper.py:19-23,100-115.
