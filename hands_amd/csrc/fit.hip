@@ -310,6 +310,7 @@ __global__ void __launch_bounds__(NT) mano_fit_kernel(Sides sides, hands_fit_cfg
     sel = w > 0.0;
     S.w[tid] = sel ? w : 0.0;
     S.sw[tid] = sel ? sqrt(w) : 0.0;
+    bad = sel && !isfinite(w);                   // a selected weight of +inf: the row is not fitted
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const float v = sel ? sd.joints[(b * 21 + tid) * 3 + c] : 0.f;
@@ -553,6 +554,7 @@ __global__ void __launch_bounds__(NT) mano_fit2d_kernel(Sides2 sides, const floa
     sel = w > 0.0;
     S.w[tid] = sel ? w : 0.0;
     E.rw[tid] = sel ? sqrt(w) : 0.0;
+    bad = sel && !isfinite(w);                   // a selected weight of +inf: the row is not fitted
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
       const float v = sel ? sd.kp2d[(b * 21 + tid) * 2 + c] : 0.f;

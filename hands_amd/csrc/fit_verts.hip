@@ -417,6 +417,7 @@ __global__ void __launch_bounds__(NT) mano_fit_verts_kernel(SidesV sides, hands_
       E.w[n] = sel ? w : 0.f;
       if (sel) {
         wsum += (double)w;
+        bad = bad || !isfinite(w);               // a selected weight of +inf: the row is not fitted
 #pragma unroll
         for (int c = 0; c < 3; ++c) bad = bad || !isfinite(sd.verts[(b * NV + n) * 3 + c]);
       }

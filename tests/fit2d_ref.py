@@ -182,7 +182,7 @@ def fit(C, y, K, w=None, valid=None, init=None, cfg=None, noise=0.0, seed=0):
     sel = w > 0
     if (valid is not None and valid == 0) or sel.sum() < 4 or not np.isfinite(y32[sel]).all() or not np.isfinite(K[:2]).all():
         return unfitted(C)
-    if not (K[0, 0] > 0 and K[1, 1] > 0):
+    if not (K[0, 0] > 0 and K[1, 1] > 0) or not np.isfinite(w[sel]).all():     # a selected weight of +inf too
         return unfitted(C)
     y = np.where(sel[:, None], y32.astype(np.float64), 0.0)                    # unweighted keypoints are never read
     w = np.where(sel, w, 0.0)                                                  # nor is a weight that is negative or no number

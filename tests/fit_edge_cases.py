@@ -265,16 +265,17 @@ def half_turn_launches(Cs):
 
 
 # ---- 6. weights that are no number, negative or -0.0 ---------------------------------------------------------------------------------
-WEIGHT_SEEDS = (21, 22, 23, 24, 25)
-WEIGHT_FITTED = (True, True, False, True, True)
+WEIGHT_SEEDS = (21, 22, 23, 24, 25, 26)
+WEIGHT_FITTED = (True, True, False, True, True, False)
 DENORMAL = 1e-40                                  # positive and below the smallest normal fp32 (1.18e-38)
 
 
 def odd_weights():
-    """(5,21) fp32.  Row 0: NaN, -1, -inf, -0.0 and a denormal among ones; row 1: four selected among NaN; row 2: three selected
+    """(6,21) fp32.  Row 0: NaN, -1, -inf, -0.0 and a denormal among ones; row 1: four selected among NaN; row 2: three selected
     among NaN (not fitted); row 3: five uneven weights among negative ones; row 4: three selected and a denormal among -0.0 --
-    the denormal is the fourth, so the row is fitted only where a denormal counts as positive."""
-    w = np.ones((5, 21), np.float32)
+    the denormal is the fourth, so the row is fitted only where a denormal counts as positive; row 5: one +inf among ones -- a
+    selected weight that is not finite, so the row is not fitted."""
+    w = np.ones((6, 21), np.float32)
     w[0, [1, 5, 19]], w[0, 8], w[0, 11], w[0, [12, 17]], w[0, 3] = NAN, -1.0, -np.inf, -0.0, DENORMAL
     w[1] = NAN
     w[1, [0, 4, 9, 18]] = 2.0
@@ -284,6 +285,7 @@ def odd_weights():
     w[3, [0, 2, 6, 13, 20]] = (0.5, 3.0, 1.0, 2.0, 0.25)
     w[4] = -0.0
     w[4, [0, 4, 13]], w[4, 18] = 2.0, DENORMAL
+    w[5, 7] = np.inf
     return w
 
 
@@ -295,7 +297,7 @@ def weight_launches(Cs):
         y3, init = _family_rows(Cs[h], WEIGHT_SEEDS, np.random.RandomState(1006), with_init)
         y3[~(w > 0)] = NAN
         rows[h] = (y3, init)
-    K = general_K(5)
+    K = general_K(len(WEIGHT_SEEDS))
     return [launch("weights3d", 3, [side(h, rows[h][0], w, rows[h][1]) for h in "rl"], F.config(iters=3)),
             launch("weights2d", 2, [side(h, project_rows(rows[h][0], K), w, rows[h][1]) for h in "rl"],
                    G.config(iters_rigid=2, iters=3), K)]
@@ -420,6 +422,7 @@ def conditions(L, Cs, key):
             assert all(r["steps"] >= 2 for r, f in zip(rr, WEIGHT_FITTED) if f), name
         w = L["sides"][0]["w"]
         assert [int((w[b] > 0).sum()) for b in (1, 2, 4)] == [4, 3, 4] and 0 < w[4, 18] < np.finfo(np.float32).tiny
+        assert np.isposinf(w[5]).sum() == 1 and np.isfinite(np.delete(w[5], 7)).all() and all(np.isfinite(s["y"][5]).all() for s in L["sides"])
         assert np.isnan(w[0]).sum() == 3 and np.signbit(w[0, 12]) and w[0, 12] == 0 and all(np.isnan(s["y"][~(w > 0)]).all() for s in L["sides"])
     elif fam in ("damping3d", "damping2d"):
         if fam == "damping3d":

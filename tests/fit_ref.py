@@ -204,8 +204,8 @@ def fit(C, y, w=None, valid=None, init=None, cfg=None, noise=0.0, seed=0):
     y32 = np.asarray(y, np.float32).reshape(21, 3)
     w = np.ones(21) if w is None else np.asarray(w, np.float32).astype(np.float64)
     sel = w > 0
-    if (valid is not None and valid == 0) or sel.sum() < 4 or not np.isfinite(y32[sel]).all():
-        return unfitted(C)
+    if (valid is not None and valid == 0) or sel.sum() < 4 or not np.isfinite(y32[sel]).all() or not np.isfinite(w[sel]).all():
+        return unfitted(C)                                                     # a selected weight of +inf too
     y = np.where(sel[:, None], y32.astype(np.float64), 0.0)                    # unweighted joints are never read
     w = np.where(sel, w, 0.0)                                                  # nor is a weight that is negative or no number
     if init is not None:

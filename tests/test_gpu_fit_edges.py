@@ -131,15 +131,17 @@ def test_half_turns_in_the_pose_prior_2d(hands, stages):
 # ---- 6. weights that are no number, negative or -0.0 ---------------------------------------------------------------------------------
 def test_weights_that_select_nothing(hands):
     """NaN, -1, -inf, -0.0 and a denormal positive weight, NaN coordinates under every joint that is not selected.  Four selected
-    joints among NaN weights are fitted, three are not (unfitted outputs, rmse NaN); a denormal is positive and counts."""
+    joints among NaN weights are fitted, three are not (unfitted outputs, rmse NaN); a denormal is positive and counts; a
+    selected weight of +inf leaves the row unfitted, with and without a caller's state."""
     for L in launches(hands, X.weight_launches):
         got, refs = run(L, hands)
         for i, g in enumerate(got):
             assert list(np.isfinite(g["rmse"])) == list(X.WEIGHT_FITTED)
             unfitted = (F if L["dim"] == 3 else G).unfitted(hands["C"][i])
-            assert g["steps"][2] == 0 and all(np.array_equal(bits(g[k][2]), bits(unfitted[k])) for k in ("pose", "beta", "transl"))
-            if L["dim"] == 2:
-                assert g["start"][2] == -1 and np.isnan(g["j3d"][2]).all() and np.isnan(g["j2d"][2]).all()
+            for b in (2, 5):
+                assert g["steps"][b] == 0 and all(np.array_equal(bits(g[k][b]), bits(unfitted[k])) for k in ("pose", "beta", "transl"))
+                if L["dim"] == 2:
+                    assert g["start"][b] == -1 and np.isnan(g["j3d"][b]).all() and np.isnan(g["j2d"][b]).all()
 
 
 # ---- 7. the damping's ends ----------------------------------------------------------------------------------------------------------
