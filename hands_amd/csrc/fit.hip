@@ -24,6 +24,9 @@
 //
 // Log / Exp, the 3 x 3 products, the tree, shape_chain, solve and the LDS state are in fit_device.h, which fit_verts.hip (the fit
 // to 778 vertices) shares; kinematics stays here: it evaluates the five tips from the tip pack, which that fit does not carry.
+// The driver is there too: the mean pose, the read of a caller's state, the `fitted` rule, the rest state, the placement of a
+// rigid alignment, the Levenberg-Marquardt stage (lm_stage) and the stores of the outputs every fit has.  A kernel here reads its
+// target, makes its start, hands lm_stage its evaluate and linearise and stores what only it has.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "hands_hip.h"
@@ -35,7 +38,7 @@ namespace {
 
 // Forward kinematics, the five tips and the pose prior's Log(Mref_j^T R_j) of state s.  Every lane of the workgroup calls it.
 template <int ROWS>
-__device__ void kinematics(Lds<ROWS>& S, const hands_mano_fit_consts& C, int s, const double* Mref, int tid) {
+__device__ __forceinline__ void kinematics(Lds<ROWS>& S, const hands_mano_fit_consts& C, int s, const double* Mref, int tid) {
   const double* R = S.R[s];
   const double* be = S.beta[s];
   if (tid < 48) {                                // rest joints of this shape
@@ -116,7 +119,7 @@ __device__ void kinematics(Lds<ROWS>& S, const hands_mano_fit_consts& C, int s, 
 }
 
 // The residual and the cost of the 3-D fit at the state kinematics() saw last (state s).
-__device__ void evaluate(Lds<NR>& S, const hands_mano_fit_consts& C, int s, double lb, double lp, int tid) {
+__device__ __forceinline__ void evaluate(Lds<NR>& S, const hands_mano_fit_consts& C, int s, double lb, double lp, int tid) {
   kinematics(S, C, s, S.M, tid);
   const double* be = S.beta[s];
   if (tid < 64) {                                // residual and cost: wave 0
@@ -218,12 +221,6 @@ __device__ __forceinline__ void shape_column(const Lds<ROWS>& S, const hands_man
   }
 }
 
-// The unknowns a stage leaves alone.  FREE_ALL: none; FREE_RIGID: all but delta_0 and t; FREE_NO_SHAPE: beta.
-enum { FREE_ALL = 0, FREE_RIGID = 1, FREE_NO_SHAPE = 2 };
-__device__ __forceinline__ bool is_frozen(int a, int mode) {
-  return mode == FREE_RIGID ? (a >= 3 && a < UT) : (mode == FREE_NO_SHAPE ? (a >= UB && a < UT) : false);
-}
-
 // g = J^T r and the damped H from the data rows in S.J, the priors included (bbar: the shape prior's reference, NULL for 0).  A
 // frozen unknown has a zero row and column, diagonal 1 (before the damping) and g = 0: its step is exactly 0 and the Cholesky
 // factor of the other unknowns is what it would be without it.
@@ -318,38 +315,16 @@ __global__ void __launch_bounds__(NT) mano_fit_kernel(Sides sides, hands_fit_cfg
       S.y[3 * tid + c] = (double)v;
     }
   }
-  if (tid >= 64 && tid < 80) {
-    const int j = tid - 64;
-    const double w[3] = {(double)C.pose_mean[3 * j], (double)C.pose_mean[3 * j + 1], (double)C.pose_mean[3 * j + 2]};
-    double E[9];
-    exp_so3(w, E);
-#pragma unroll
-    for (int k = 0; k < 9; ++k) S.M[9 * j + k] = E[k];
-  }
-  if (sd.init_pose && tid < 157) {               // a caller's initial state
-    const float v = tid < 144 ? sd.init_pose[b * 144 + tid] : (tid < 154 ? sd.init_beta[b * 10 + tid - 144] : sd.init_transl[b * 3 + tid - 154]);
-    bad = bad || !isfinite(v);
-    if (tid < 144) S.R[0][tid] = (double)v;
-    else if (tid < 154) S.beta[0][tid - 144] = (double)v;
-    else S.t[0][tid - 154] = (double)v;
-  }
+  mean_pose(S, C.pose_mean, tid);
+  bad = read_init(S, sd, b, tid) || bad;         // a caller's initial state
   const int nsel = __syncthreads_count(sel);
-  const bool any_bad = __syncthreads_or(bad);
-  const bool fitted = (sd.valid ? sd.valid[b] != 0.f : true) && nsel >= 4 && !any_bad;
-  if (!fitted) {                                 // the whole workgroup leaves: pose (I, M_1..M_15), zeros, NaN, no step
-    if (tid < 144) sd.pose[b * 144 + tid] = (float)S.M[tid];
-    else if (tid < 154) sd.beta[b * 10 + tid - 144] = 0.f;
-    else if (tid < 157) sd.transl[b * 3 + tid - 154] = 0.f;
-    else if (tid == 157) sd.rmse[b] = __builtin_nanf("");
-    else if (tid == 158) sd.steps[b] = 0;
+  if (!row_fitted(sd, b, nsel, bad)) {           // the whole workgroup leaves
+    store_unfitted(S, sd, b, tid);
     return;
   }
 
   if (!sd.init_pose) {                           // the rest hand, aligned rigidly to the target
-    if (tid < 144) S.R[0][tid] = S.M[tid];
-    else if (tid < 154) S.beta[0][tid - 144] = 0.0;
-    else if (tid < 157) S.t[0][tid - 154] = 0.0;
-    __syncthreads();
+    rest_state(S, tid);
     evaluate(S, C, 0, lb, lp, tid);
     if (tid == 0) {
       double sw = 0.0, mx[3] = {0.0, 0.0, 0.0}, my[3] = {0.0, 0.0, 0.0};
@@ -372,68 +347,17 @@ __global__ void __launch_bounds__(NT) mano_fit_kernel(Sides sides, hands_fit_cfg
           }
       double Rm[3][3], scale;
       procrustes_solve(K, var1, Rm, &scale);     // the scale is not used: the alignment is rigid
-      for (int a = 0; a < 3; ++a) {              // MANO turns about the wrist joint J_0: y ~ Rm (x - J_0) + J_0 + t
-        const double e0 = mx[0] - S.Jr[0], e1 = mx[1] - S.Jr[1], e2 = mx[2] - S.Jr[2];
-        S.t[0][a] = (my[a] - ((Rm[a][0] * e0 + Rm[a][1] * e1) + Rm[a][2] * e2)) - S.Jr[a];
-        for (int c = 0; c < 3; ++c) S.R[0][3 * a + c] = Rm[a][c];
-      }
+      place_rigid(S, Rm, mx, my);
     }
   }
   __syncthreads();
 
-  // `fresh`: what evaluate() left in LDS belongs to the current state -- after an accepted step it does, the candidate having
-  // become the current state, and the evaluation is not repeated (it would give the same bits)
-  double mu = cfg.mu0, c0 = 0.0;
+  double c0 = 0.0;
   int steps = 0;
   bool fresh = false;
-  for (int it = 0; it < cfg.iters; ++it) {
-    if (!fresh) {
-      evaluate(S, C, 0, lb, lp, tid);
-      c0 = S.c[0];
-    }
-    linearise(S, C, 0, lb, lp, mu, tid);
-    const bool ok = solve(S, tid);
-    if (tid < 16) {                              // the candidate: R_j Exp(delta_j), beta + delta_beta, t + delta_t
-      const double w[3] = {S.d[3 * tid], S.d[3 * tid + 1], S.d[3 * tid + 2]};
-      double E[9], Rn[9];
-      exp_so3(w, E);
-      mul_nn(S.R[0] + 9 * tid, E, Rn);
-#pragma unroll
-      for (int k = 0; k < 9; ++k) S.R[1][9 * tid + k] = Rn[k];
-    } else if (tid >= 64 && tid < 74) {
-      S.beta[1][tid - 64] = S.beta[0][tid - 64] + S.d[UB + tid - 64];
-    } else if (tid >= 74 && tid < 77) {
-      S.t[1][tid - 74] = S.t[0][tid - 74] + S.d[UT + tid - 74];
-    }
-    __syncthreads();
-    evaluate(S, C, 1, lb, lp, tid);
-    const double c1 = S.c[0];
-    const bool accept = ok && c1 < c0;           // strict, false for NaN; the same on every lane
-    fresh = accept;
-    if (accept) {
-      c0 = c1;
-      if (tid < 144) S.R[0][tid] = S.R[1][tid];
-      else if (tid < 154) S.beta[0][tid - 144] = S.beta[1][tid - 144];
-      else if (tid < 157) S.t[0][tid - 154] = S.t[1][tid - 154];
-      mu = fmax(mu / 3.0, MU_MIN);
-      ++steps;
-    } else {
-      mu = fmin(5.0 * mu, MU_MAX);
-    }
-    __syncthreads();
-  }
-  if (!fresh) evaluate(S, C, 0, lb, lp, tid);
-
-  if (tid < 144) sd.pose[b * 144 + tid] = (float)S.R[0][tid];
-  else if (tid < 154) sd.beta[b * 10 + tid - 144] = (float)S.beta[0][tid - 144];
-  else if (tid < 157) sd.transl[b * 3 + tid - 154] = (float)S.t[0][tid - 154];
-  else if (tid == 157) {
-    double sw = 0.0;
-    for (int k = 0; k < 21; ++k) sw += S.w[k];
-    sd.rmse[b] = (float)sqrt(S.c[1] / sw);
-  } else if (tid == 158) {
-    sd.steps[b] = steps;
-  }
+  lm_stage(S, cfg.iters, FREE_ALL, cfg.mu0, c0, steps, fresh, tid, [&](int s) { evaluate(S, C, s, lb, lp, tid); },
+           [&](double mu, int) { linearise(S, C, 0, lb, lp, mu, tid); });
+  store_fitted(S, sd, b, steps, tid, [&] { return weight_sum(S); });
 }
 
 // ---- the fit to 2-D keypoints (hands_mano_fit2d_f32; DESIGN.md section 7 "MANO fitting to 2-D keypoints") ----------------------
@@ -448,7 +372,7 @@ struct Cam {                                     // what the 2-D fit keeps besid
 };
 
 // Projection, residual, row scales and cost of state s; +inf where a weighted joint is not in front of z_min.
-__device__ void evaluate2d(Lds<NR2>& S, Cam& E, const hands_mano_fit_consts& C, int s, double lb, double lp, int tid) {
+__device__ __forceinline__ void evaluate2d(Lds<NR2>& S, Cam& E, const hands_mano_fit_consts& C, int s, double lb, double lp, int tid) {
   kinematics(S, C, s, E.Mbar, tid);
   if (tid < 64) {                                // wave 0
     double rho = 0.0, we2 = 0.0;
@@ -569,6 +493,8 @@ __global__ void __launch_bounds__(NT) mano_fit2d_kernel(Sides2 sides, const floa
     E.sig2 = cfg.robust_sigma * cfg.robust_sigma;
     E.zmin = cfg.z_min;
   }
+  // mean_pose, read_init and row_fitted of fit_device.h, written out: through the three calls this kernel was 1.5 to 2.9 % slower
+  // (docs/EXPERIMENTS.md), so the text stays here until that is understood
   if (tid >= 64 && tid < 80) {
     const int j = tid - 64;
     const double w[3] = {(double)C.pose_mean[3 * j], (double)C.pose_mean[3 * j + 1], (double)C.pose_mean[3 * j + 2]};
@@ -594,10 +520,7 @@ __global__ void __launch_bounds__(NT) mano_fit2d_kernel(Sides2 sides, const floa
     if (tid < 144) E.Mbar[tid] = own ? S.R[0][tid] : S.M[tid];
     else if (tid < 154) E.bbar[tid - 144] = own ? S.beta[0][tid - 144] : 0.0;
     if (!sd.init_pose) {                         // the rest hand under the best of the 24 axis-aligned rotations, weak perspective
-      if (tid < 144) S.R[0][tid] = S.M[tid];
-      else if (tid < 154) S.beta[0][tid - 144] = 0.0;
-      else if (tid < 157) S.t[0][tid - 154] = 0.0;
-      __syncthreads();
+      rest_state(S, tid);
       kinematics(S, C, 0, E.Mbar, tid);
       if (tid < 21) {                            // n_k = K[:2,:2]^-1 (y_k - K[:2,2]), kept in E.uv
         const double det = E.K[0] * E.K[4] - E.K[1] * E.K[3];
@@ -673,94 +596,34 @@ __global__ void __launch_bounds__(NT) mano_fit2d_kernel(Sides2 sides, const floa
   }
   __syncthreads();                               // E.Mbar, E.bbar and the start state are complete
 
-  // `fresh`: what evaluate2d() left in LDS belongs to the current state, as in the 3-D kernel
   double c0 = 0.0;
   int steps = 0;
-  bool fresh = true;
+  bool fresh = true;                             // the first evaluation is the depth guard's
   if (fitted) {
     evaluate2d(S, E, C, 0, lb, lp, tid);
     c0 = S.c[0];
     fitted = c0 < (double)INFINITY;              // the depth guard on the initial state
   }
-  if (!fitted) {                                 // the whole workgroup: pose (I, M_1..M_15), zeros, NaN, no step
+  if (!fitted) {                                 // the whole workgroup leaves; NaN in j3d and j2d
     const float nanf_ = __builtin_nanf("");
-    if (tid < 144) sd.pose[b * 144 + tid] = (float)S.M[tid];
-    else if (tid < 154) sd.beta[b * 10 + tid - 144] = 0.f;
-    else if (tid < 157) sd.transl[b * 3 + tid - 154] = 0.f;
-    else if (tid == 157) sd.rmse[b] = nanf_;
-    else if (tid == 158) sd.steps[b] = 0;
-    else if (tid == 159) sd.start[b] = -1;
+    store_unfitted(S, sd, b, tid);
+    if (tid == 159) sd.start[b] = -1;
     if (tid < 63) sd.j3d[b * 63 + tid] = nanf_;
     else if (tid >= 64 && tid < 106) sd.j2d[b * 42 + tid - 64] = nanf_;
     return;
   }
 
-  for (int stage = 0; stage < 2; ++stage) {
-    const int n = stage == 0 ? cfg.iters_rigid : cfg.iters;
-    const int mode = stage == 0 ? FREE_RIGID : (cfg.fit_shape ? FREE_ALL : FREE_NO_SHAPE);
-    double mu = cfg.mu0;
-    for (int it = 0; it < n; ++it) {
-      if (!fresh) {
-        evaluate2d(S, E, C, 0, lb, lp, tid);
-        c0 = S.c[0];
-      }
-      linearise2d(S, E, C, 0, lb, lp, mu, mode, tid);
-      const bool ok = solve(S, tid);
-      if (tid < 16) {                            // the candidate; a frozen rotation is copied, so that it keeps its bits
-        double Rn[9];
-        if (is_frozen(3 * tid, mode)) {
-#pragma unroll
-          for (int k = 0; k < 9; ++k) Rn[k] = S.R[0][9 * tid + k];
-        } else {
-          const double w[3] = {S.d[3 * tid], S.d[3 * tid + 1], S.d[3 * tid + 2]};
-          double X[9];
-          exp_so3(w, X);
-          mul_nn(S.R[0] + 9 * tid, X, Rn);
-        }
-#pragma unroll
-        for (int k = 0; k < 9; ++k) S.R[1][9 * tid + k] = Rn[k];
-      } else if (tid >= 64 && tid < 74) {
-        S.beta[1][tid - 64] = S.beta[0][tid - 64] + S.d[UB + tid - 64];
-      } else if (tid >= 74 && tid < 77) {
-        S.t[1][tid - 74] = S.t[0][tid - 74] + S.d[UT + tid - 74];
-      }
-      __syncthreads();
-      evaluate2d(S, E, C, 1, lb, lp, tid);
-      const double c1 = S.c[0];
-      const bool accept = ok && c1 < c0;         // strict, false for NaN and for +inf (the depth guard)
-      fresh = accept;
-      if (accept) {
-        c0 = c1;
-        if (tid < 144) S.R[0][tid] = S.R[1][tid];
-        else if (tid < 154) S.beta[0][tid - 144] = S.beta[1][tid - 144];
-        else if (tid < 157) S.t[0][tid - 154] = S.t[1][tid - 154];
-        mu = fmax(mu / 3.0, MU_MIN);
-        ++steps;
-      } else {
-        mu = fmin(5.0 * mu, MU_MAX);
-      }
-      __syncthreads();
-    }
-  }
-  if (!fresh) evaluate2d(S, E, C, 0, lb, lp, tid);
+  // the rigid stage, then the full one; the depth guard (+inf cost) keeps a candidate from being accepted
+  for (int stage = 0; stage < 2; ++stage)
+    lm_stage(S, stage == 0 ? cfg.iters_rigid : cfg.iters, stage == 0 ? FREE_RIGID : (cfg.fit_shape ? FREE_ALL : FREE_NO_SHAPE),
+             cfg.mu0, c0, steps, fresh, tid, [&](int s) { evaluate2d(S, E, C, s, lb, lp, tid); },
+             [&](double mu, int mode) { linearise2d(S, E, C, 0, lb, lp, mu, mode, tid); });
 
-  if (tid < 144) sd.pose[b * 144 + tid] = (float)S.R[0][tid];
-  else if (tid < 154) sd.beta[b * 10 + tid - 144] = (float)S.beta[0][tid - 144];
-  else if (tid < 157) sd.transl[b * 3 + tid - 154] = (float)S.t[0][tid - 154];
-  else if (tid == 157) {
-    double sw = 0.0;
-    for (int k = 0; k < 21; ++k) sw += S.w[k];
-    sd.rmse[b] = (float)sqrt(S.c[1] / sw);
-  } else if (tid == 158) {
-    sd.steps[b] = steps;
-  } else if (tid == 159) {
-    sd.start[b] = start;
-  }
+  store_fitted(S, sd, b, steps, tid, [&] { return weight_sum(S); });
+  if (tid == 159) sd.start[b] = start;
   if (tid < 63) sd.j3d[b * 63 + tid] = (float)E.X[tid];
   else if (tid >= 64 && tid < 106) sd.j2d[b * 42 + tid - 64] = (float)E.uv[tid - 64];
 }
-
-bool non_negative(double v) { return isfinite(v) && v >= 0.0; }
 
 bool consts_given(const hands_mano_fit_consts& c) {
   return c.pose_mean && c.J_template && c.J_shapedirs && c.tip_v_template && c.tip_shapedirs && c.tip_lbs_weights && c.tip_posedirs;
@@ -770,16 +633,11 @@ bool consts_given(const hands_mano_fit_consts& c) {
 
 extern "C" int hands_mano_fit_f32(const hands_mano_fit_side* sides, int n_sides, const hands_fit_cfg* cfg, int B,
                                   hands_stream_t stream) {
-  if (!sides || !cfg || n_sides < 1 || n_sides > 2 || B <= 0 || cfg->iters < 0) return HANDS_EINVAL;
-  if (!non_negative(cfg->lambda_beta) || !non_negative(cfg->lambda_pose) || !non_negative(cfg->mu0)) return HANDS_EINVAL;
+  if (!sides || !cfg || n_sides < 1 || n_sides > 2 || B <= 0 || !fit_cfg_ok(*cfg)) return HANDS_EINVAL;
   Sides k;
   for (int i = 0; i < 2; ++i) {
-    k.s[i] = sides[i < n_sides ? i : 0];
-    const hands_mano_fit_side& d = k.s[i];
-    if (!consts_given(d.consts)) return HANDS_EINVAL;
-    if (!d.joints || !d.pose || !d.beta || !d.transl || !d.rmse || !d.steps) return HANDS_EINVAL;
-    const int given = (d.init_pose != nullptr) + (d.init_beta != nullptr) + (d.init_transl != nullptr);
-    if (given != 0 && given != 3) return HANDS_EINVAL;
+    const hands_mano_fit_side& d = k.s[i] = sides[i < n_sides ? i : 0];
+    if (!consts_given(d.consts) || !fit_side_ok(d, {d.joints, d.pose, d.beta, d.transl, d.rmse, d.steps})) return HANDS_EINVAL;
   }
   hipLaunchKernelGGL(mano_fit_kernel, dim3(B, n_sides), dim3(NT), 0, (hipStream_t)stream, k, *cfg);
   HANDS_LAUNCH_CHECK();
@@ -787,17 +645,13 @@ extern "C" int hands_mano_fit_f32(const hands_mano_fit_side* sides, int n_sides,
 
 extern "C" int hands_mano_fit2d_f32(const hands_mano_fit2d_side* sides, int n_sides, const float* K, const hands_fit2d_cfg* cfg,
                                     int B, hands_stream_t stream) {
-  if (!sides || !cfg || !K || n_sides < 1 || n_sides > 2 || B <= 0 || cfg->iters < 0 || cfg->iters_rigid < 0) return HANDS_EINVAL;
-  if (!non_negative(cfg->lambda_beta) || !non_negative(cfg->lambda_pose) || !non_negative(cfg->mu0)) return HANDS_EINVAL;
+  if (!sides || !cfg || !K || n_sides < 1 || n_sides > 2 || B <= 0 || !fit_cfg_ok(*cfg) || cfg->iters_rigid < 0) return HANDS_EINVAL;
   if (!non_negative(cfg->robust_sigma) || !isfinite(cfg->z_min) || !(cfg->z_min > 0.0)) return HANDS_EINVAL;
   Sides2 k;
   for (int i = 0; i < 2; ++i) {
-    k.s[i] = sides[i < n_sides ? i : 0];
-    const hands_mano_fit2d_side& d = k.s[i];
-    if (!consts_given(d.consts)) return HANDS_EINVAL;
-    if (!d.kp2d || !d.pose || !d.beta || !d.transl || !d.rmse || !d.steps || !d.start || !d.j3d || !d.j2d) return HANDS_EINVAL;
-    const int given = (d.init_pose != nullptr) + (d.init_beta != nullptr) + (d.init_transl != nullptr);
-    if (given != 0 && given != 3) return HANDS_EINVAL;
+    const hands_mano_fit2d_side& d = k.s[i] = sides[i < n_sides ? i : 0];
+    if (!consts_given(d.consts) || !fit_side_ok(d, {d.kp2d, d.pose, d.beta, d.transl, d.rmse, d.steps, d.start, d.j3d, d.j2d}))
+      return HANDS_EINVAL;
   }
   hipLaunchKernelGGL(mano_fit2d_kernel, dim3(B, n_sides), dim3(NT), 0, (hipStream_t)stream, k, K, *cfg);
   HANDS_LAUNCH_CHECK();

@@ -12,8 +12,10 @@
 // A tile is 48 rows x 64 columns in LDS; the four waves then add the lower-triangle 16 x 16 blocks of its Gram matrix with
 // v_mfma_f64_16x16x4_f64, ten blocks, each owned by one wave for the whole walk, tiles and rows in ascending order.  Both operands
 // of a block are 16 consecutive doubles of a tile row, so one LDS read serves J^T and J.  The Gram matrix holds H's data part and
-// g = J^T r (row 61); priors and damping go on as in fit.hip and its solve() factors.  A candidate costs one walk without the
-// Jacobian; after an accepted step that evaluation is kept.
+// g = J^T r (row 61); priors and damping go on as in fit.hip and solve() of fit_device.h factors.  A candidate costs one walk without
+// the Jacobian; after an accepted step that evaluation is kept.  The set-up of the state and the stores the three fits share are
+// the driver routines of fit_device.h; the iteration is this kernel's own copy of lm_stage with FREE_ALL: called through
+// lm_stage the same arithmetic was 5 % slower (docs/EXPERIMENTS.md), so the text stays here until that is understood.
 // Every sum has an order the code fixes: the butterflies (DPP row moves) add the same pairs on every lane, a vertex slot adds its
 // 49 tiles in ascending order, one lane adds the 16 slots.  kinematics() of fit.hip is not used: it evaluates the tips from the tip pack;
 // here joint_state() leaves the joints and the walk delivers the five tip vertices.  62 KB of LDS.
@@ -424,31 +426,11 @@ __global__ void __launch_bounds__(NT) mano_fit_verts_kernel(SidesV sides, hands_
     }
     nsel += __syncthreads_count(sel);
   }
-  if (tid >= 64 && tid < 80) {
-    const int j = tid - 64;
-    const double w[3] = {(double)C.pose_mean[3 * j], (double)C.pose_mean[3 * j + 1], (double)C.pose_mean[3 * j + 2]};
-    double X[9];
-    exp_so3(w, X);
-#pragma unroll
-    for (int k = 0; k < 9; ++k) S.M[9 * j + k] = X[k];
-  }
-  if (sd.init_pose && tid < 157) {               // a caller's initial state
-    const float v = tid < 144 ? sd.init_pose[b * 144 + tid] : (tid < 154 ? sd.init_beta[b * 10 + tid - 144] : sd.init_transl[b * 3 + tid - 154]);
-    bad = bad || !isfinite(v);
-    if (tid < 144) S.R[0][tid] = (double)v;
-    else if (tid < 154) S.beta[0][tid - 144] = (double)v;
-    else S.t[0][tid - 154] = (double)v;
-  }
-  const bool any_bad = __syncthreads_or(bad);
-  const bool fitted = (sd.valid ? sd.valid[b] != 0.f : true) && nsel >= 4 && !any_bad;
-  if (!fitted) {                                 // the whole workgroup leaves: pose (I, M_1..M_15), zeros, NaN, no step
-    const float nanf_ = __builtin_nanf("");
-    if (tid < 144) sd.pose[b * 144 + tid] = (float)S.M[tid];
-    else if (tid < 154) sd.beta[b * 10 + tid - 144] = 0.f;
-    else if (tid < 157) sd.transl[b * 3 + tid - 154] = 0.f;
-    else if (tid == 157) sd.rmse[b] = nanf_;
-    else if (tid == 158) sd.steps[b] = 0;
-    if (tid < 63) sd.j3d[b * 63 + tid] = nanf_;
+  mean_pose(S, C.pose_mean, tid);
+  bad = read_init(S, sd, b, tid) || bad;         // a caller's initial state
+  if (!row_fitted(sd, b, nsel, bad)) {           // the whole workgroup leaves; NaN in j3d
+    store_unfitted(S, sd, b, tid);
+    if (tid < 63) sd.j3d[b * 63 + tid] = __builtin_nanf("");
     return;
   }
   {
@@ -457,10 +439,7 @@ __global__ void __launch_bounds__(NT) mano_fit_verts_kernel(SidesV sides, hands_
   }
 
   if (!sd.init_pose) {                           // the rest hand, its vertices aligned rigidly to the weighted target vertices
-    if (tid < 144) S.R[0][tid] = S.M[tid];
-    else if (tid < 154) S.beta[0][tid - 144] = 0.0;
-    else if (tid < 157) S.t[0][tid - 154] = 0.0;
-    __syncthreads();
+    rest_state(S, tid);
     joint_state(S, C, 0, tid);
     walk<REST>(S, E, sd, b, 0, tid, nullptr);
     double m[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -496,16 +475,13 @@ __global__ void __launch_bounds__(NT) mano_fit_verts_kernel(SidesV sides, hands_
       for (int a = 0; a < 3; ++a)
         for (int c = 0; c < 3; ++c) K[a][c] = k9[3 * a + c];
       procrustes_solve(K, 1.0, Rm, &scale);      // the scale is not used: the alignment is rigid
-      for (int a = 0; a < 3; ++a) {              // MANO turns about the wrist joint J_0: y ~ Rm (x - J_0) + J_0 + t
-        const double e0 = m[0] - S.Jr[0], e1 = m[1] - S.Jr[1], e2 = m[2] - S.Jr[2];
-        S.t[0][a] = (m[3 + a] - ((Rm[a][0] * e0 + Rm[a][1] * e1) + Rm[a][2] * e2)) - S.Jr[a];
-        for (int c = 0; c < 3; ++c) S.R[0][3 * a + c] = Rm[a][c];
-      }
+      place_rigid(S, Rm, m, m + 3);
     }
   }
   __syncthreads();
 
-  // `fresh`: what evaluate_verts() left in LDS belongs to the current state, as in fit.hip
+  // lm_stage of fit_device.h with FREE_ALL, written out (see the head of the file); `fresh`: what evaluate_verts() left in LDS
+  // belongs to the current state
   double mu = cfg.mu0, c0 = 0.0;
   int steps = 0;
   bool fresh = false;
@@ -547,32 +523,22 @@ __global__ void __launch_bounds__(NT) mano_fit_verts_kernel(SidesV sides, hands_
   }
   if (!fresh) evaluate_verts(S, E, sd, b, 0, lb, lp, tid);
 
-  if (tid < 144) sd.pose[b * 144 + tid] = (float)S.R[0][tid];
-  else if (tid < 154) sd.beta[b * 10 + tid - 144] = (float)S.beta[0][tid - 144];
-  else if (tid < 157) sd.transl[b * 3 + tid - 154] = (float)S.t[0][tid - 154];
-  else if (tid == 157) sd.rmse[b] = (float)sqrt(S.c[1] / E.sumw);
-  else if (tid == 158) sd.steps[b] = steps;
+  store_fitted(S, sd, b, steps, tid, [&] { return E.sumw; });
   if (tid < 63) sd.j3d[b * 63 + tid] = (float)(S.joints[tid] + S.t[0][tid % 3]);
 }
-
-bool non_negative(double v) { return isfinite(v) && v >= 0.0; }
 
 }  // namespace
 
 extern "C" int hands_mano_fit_verts_f32(const hands_mano_fit_verts_side* sides, int n_sides, const hands_fit_cfg* cfg, int B,
                                         hands_stream_t stream) {
-  if (!sides || !cfg || n_sides < 1 || n_sides > 2 || B <= 0 || cfg->iters < 0) return HANDS_EINVAL;
-  if (!non_negative(cfg->lambda_beta) || !non_negative(cfg->lambda_pose) || !non_negative(cfg->mu0)) return HANDS_EINVAL;
+  if (!sides || !cfg || n_sides < 1 || n_sides > 2 || B <= 0 || !fit_cfg_ok(*cfg)) return HANDS_EINVAL;
   SidesV k;
   for (int i = 0; i < 2; ++i) {
-    k.s[i] = sides[i < n_sides ? i : 0];
-    const hands_mano_fit_verts_side& d = k.s[i];
+    const hands_mano_fit_verts_side& d = k.s[i] = sides[i < n_sides ? i : 0];
     const hands_mano_fit_verts_consts& c = d.consts;
-    if (!c.pose_mean || !c.J_template || !c.J_shapedirs || !c.v_template || !c.shapedirs || !c.lbs_weights || !c.posedirs_vm)
+    if (!fit_side_ok(d, {c.pose_mean, c.J_template, c.J_shapedirs, c.v_template, c.shapedirs, c.lbs_weights, c.posedirs_vm, d.verts,
+                         d.pose, d.beta, d.transl, d.rmse, d.steps, d.j3d}))
       return HANDS_EINVAL;
-    if (!d.verts || !d.pose || !d.beta || !d.transl || !d.rmse || !d.steps || !d.j3d) return HANDS_EINVAL;
-    const int given = (d.init_pose != nullptr) + (d.init_beta != nullptr) + (d.init_transl != nullptr);
-    if (given != 0 && given != 3) return HANDS_EINVAL;
   }
   hipLaunchKernelGGL(mano_fit_verts_kernel, dim3(B, n_sides), dim3(NT), 0, (hipStream_t)stream, k, *cfg);
   HANDS_LAUNCH_CHECK();

@@ -23,6 +23,7 @@ fits no scale.
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 from dataclasses import dataclass
 
 import torch
@@ -59,13 +60,20 @@ class FitConfig:
     mu0: float = 1e-3
 
     def c_struct(self) -> FitCfg:
-        if int(self.iters) != self.iters or self.iters < 0:
-            raise ValueError(f"hands_amd: iters is a non-negative integer, got {self.iters!r}")
-        for name in ("lambda_beta", "lambda_pose", "mu0"):
-            v = float(getattr(self, name))
-            if not (v >= 0.0 and v != float("inf")):
-                raise ValueError(f"hands_amd: {name} is finite and not negative, got {v!r}")
+        _check_config(self, ("iters",), ("lambda_beta", "lambda_pose", "mu0"))
         return FitCfg(int(self.iters), float(self.lambda_beta), float(self.lambda_pose), float(self.mu0))
+
+
+def _check_config(config, counts, reals):
+    """ValueError unless the fields ``counts`` are non-negative integers and the fields ``reals`` finite and not negative."""
+    for name in counts:
+        v = getattr(config, name)
+        if int(v) != v or v < 0:
+            raise ValueError(f"hands_amd: {name} is a non-negative integer, got {v!r}")
+    for name in reals:
+        v = float(getattr(config, name))
+        if not (v >= 0.0 and v != float("inf")):
+            raise ValueError(f"hands_amd: {name} is finite and not negative, got {v!r}")
 
 
 def _device_of(t, what):
@@ -101,39 +109,83 @@ def _opt(v, shape, dev, what):
     return v
 
 
-def _launch(packs, joints, weights, valids, inits, config, dev):
-    """One hands_mano_fit_f32 launch over len(packs) sides of B rows; -> per side (pose, beta, transl, rmse, steps)."""
-    n, B = len(packs), joints[0].shape[0]
-    sides, outs, keep = (ManoFitSide * n)(), [], []
+_Fit = namedtuple("_Fit", "entry side consts const_keys data data_shape n_weights extras config shared", defaults=((),))
+"""What tells one fit from another on the way to its C entry: the entry's name, the ctypes side and consts structs, the keys of
+the pack the consts are, name and per-row shape of the data tensor, the number of weights of a row, the outputs behind pose,
+beta, transl, rmse and steps as (name, per-row shape, dtype), the configuration class, and the tensors the entry takes once for
+all sides as (name, per-row shape)."""
+
+_OUTPUTS = (("pose", (16, 3, 3), torch.float32), ("beta", (10,), torch.float32), ("transl", (3,), torch.float32),
+            ("rmse", (), torch.float32), ("steps", (), torch.int32))
+_FIT_JOINTS = _Fit("hands_mano_fit_f32", ManoFitSide, ManoFitConsts, _CONST_KEYS, "joints", (21, 3), 21, (), FitConfig)
+
+
+def _launch(fit, packs, data, weights, valids, inits, cfg, dev, shared=()):
+    """One launch of ``fit.entry`` over len(packs) sides of B rows; -> per side the outputs, _OUTPUTS then ``fit.extras``."""
+    n, B = len(packs), data[0].shape[0]
+    shared = [_opt(t, (B,) + s, dev, k) for t, (k, s) in zip(shared, fit.shared)]
+    sides, outs, keep = (fit.side * n)(), [], []
     for i in range(n):
-        j = _opt(joints[i], (B, 21, 3), dev, "joints")
-        w, v = _opt(weights[i], (B, 21), dev, "weights"), _opt(valids[i], (B,), dev, "valid")
+        y = _opt(data[i], (B,) + fit.data_shape, dev, fit.data)
+        w, v = _opt(weights[i], (B, fit.n_weights), dev, "weights"), _opt(valids[i], (B,), dev, "valid")
         init = (None, None, None)
         if inits[i] is not None:
-            init = tuple(_opt(a, s, dev, "init " + k) for a, s, k in zip(inits[i], ((B, 16, 3, 3), (B, 10), (B, 3)),
-                                                                         ("pose", "beta", "transl")))
+            if len(inits[i]) == 3:
+                init = tuple(_opt(a, (B,) + s, dev, "init " + k) for a, (k, s, _) in zip(inits[i], _OUTPUTS))
             if any(a is None for a in init):
                 raise ValueError("hands_amd: init is (pose (B,16,3,3), beta (B,10), transl (B,3)), all three")
-        o = (torch.empty(B, 16, 3, 3, device=dev), torch.empty(B, 10, device=dev), torch.empty(B, 3, device=dev),
-             torch.empty(B, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
-        consts = ManoFitConsts(*[ptr(packs[i][k]) for k in _CONST_KEYS])
-        sides[i] = ManoFitSide(consts, ptr(j), ptr(w), ptr(v), ptr(init[0]), ptr(init[1]), ptr(init[2]), *[ptr(t) for t in o])
+        o = [torch.empty((B,) + s, dtype=t, device=dev) for _, s, t in _OUTPUTS + fit.extras]
+        consts = fit.consts(*[ptr(packs[i][k]) for k in fit.const_keys])
+        sides[i] = fit.side(consts, ptr(y), ptr(w), ptr(v), *[ptr(t) for t in init], *[ptr(t) for t in o])
         outs.append(o)
-        keep.append((j, w, v, init))           # converted copies stay alive until the launch is queued
-    cfg = (config or FitConfig()).c_struct()
-    check(_lib.lib().hands_mano_fit_f32(sides, n, C.byref(cfg), B, torch.cuda.current_stream(dev).cuda_stream), "hands_mano_fit_f32")
+        keep.append((y, w, v, init))           # converted copies stay alive until the launch is queued
+    check(getattr(_lib.lib(), fit.entry)(sides, n, *[ptr(t) for t in shared], C.byref(cfg), B,
+                                         torch.cuda.current_stream(dev).cuda_stream), fit.entry)
     return outs
 
 
-def _result(pack, out):
-    """pose, beta, transl, rmse, steps and pose_aa (B,48) = [Log R_0, Log R_j - hands_mean_j], the axis-angle form
-    HandsWrapper.process_data and the reference's targets use."""
-    pose = out[0]
-    aa = torch.empty(pose.shape[0], 48, device=pose.device)
-    check(_lib.lib().hands_matrix_to_axis_angle_f32(ptr(pose), ptr(aa), pose.shape[0] * 16,
-                                                    torch.cuda.current_stream(pose.device).cuda_stream), "matrix_to_axis_angle")
-    return xdict({"pose": pose, "beta": out[1], "transl": out[2], "rmse": out[3], "steps": out[4],
-                  "pose_aa": aa - pack["pose_mean"]})
+def _matrix_to_aa(rot):
+    """(B,16,3,3) -> (B,48) axis-angle through hands_matrix_to_axis_angle_f32."""
+    aa = torch.empty(rot.shape[0], 48, device=rot.device)
+    check(_lib.lib().hands_matrix_to_axis_angle_f32(ptr(rot), ptr(aa), rot.shape[0] * 16,
+                                                    torch.cuda.current_stream(rot.device).cuda_stream), "matrix_to_axis_angle")
+    return aa
+
+
+def _result(fit, pack, out):
+    """The outputs by name, in the order of the launch, then pose_aa (B,48) = [Log R_0, Log R_j - hands_mean_j], the axis-angle
+    form HandsWrapper.process_data and the reference's targets use."""
+    r = xdict({name: t for (name, _, _), t in zip(_OUTPUTS + fit.extras, out)})
+    r["pose_aa"] = _matrix_to_aa(out[0]) - pack["pose_mean"]
+    return r
+
+
+def _fit(fit, what, hands, model_or_layer, data, weights, valids, inits, config, shared=()):
+    """The fit of the sides ``hands`` (("r",), ("l",) or "rl") in one launch; -> per side what the public functions return."""
+    cfg = (config or fit.config()).c_struct()      # a bad configuration is refused before anything else is looked at
+    dev = _device_of(data[0], what)
+    packs = [_mano_pack(model_or_layer, h, dev) for h in hands]
+    outs = _launch(fit, packs, data, weights, valids, inits, cfg, dev, shared)
+    return tuple(_result(fit, p, o) for p, o in zip(packs, outs))
+
+
+_TARGET_KEYS = (("mano.pose", "pose_aa"), ("mano.beta", "beta"), ("mano.fit.rmse", "rmse"), ("mano.fit.transl", "transl"))
+
+
+def _valid_flags(meta_info):
+    """[right_valid, left_valid] of ``meta_info``, None where it has none."""
+    return [meta_info[k] if meta_info is not None and k in meta_info else None for k in ("right_valid", "left_valid")]
+
+
+def _with_fits(targets, fits, keys, keep=()):
+    """A NEW xdict with the entries of ``targets`` in which, for hand h and every (key, name) of ``keys``, ``key.h`` is ``name``
+    of that hand's fit; a key of ``keep`` that ``targets`` has is left alone."""
+    out = xdict(targets)
+    for h, f in zip("rl", fits):
+        for key, name in keys:
+            if not (key in keep and f"{key}.{h}" in targets):
+                out.overwrite(f"{key}.{h}", f[name])
+    return out
 
 
 def fit_mano(joints, model_or_layer, side="r", weights=None, valid=None, init=None, config=None) -> xdict:
@@ -147,18 +199,14 @@ def fit_mano(joints, model_or_layer, side="r", weights=None, valid=None, init=No
     the rotation BEFORE the MANO head adds pose_mean to its axis-angle: hand ``pose_aa`` on, not ``pose``), ``beta`` (B,10),
     ``transl`` (B,3) -- the model's joints plus ``transl`` approximate ``joints`` --, ``rmse`` (B) in metres without the priors, ``steps`` (B) int32 accepted steps and ``pose_aa`` (B,48).  A row that is not fitted (``valid`` 0, fewer
     than four weighted joints, a non-finite weighted joint or initial value) has the mean pose, zeros, ``rmse`` NaN, 0 steps."""
-    dev = _device_of(joints, "fit_mano")
-    pack = _mano_pack(model_or_layer, side, dev)
-    return _result(pack, _launch([pack], [joints], [weights], [valid], [init], config, dev)[0])
+    return _fit(_FIT_JOINTS, "fit_mano", (side,), model_or_layer, [joints], [weights], [valid], [init], config)[0]
 
 
 def fit_mano_hands(joints_r, joints_l, model, weights_r=None, weights_l=None, valid_r=None, valid_l=None, init_r=None,
                    init_l=None, config=None):
     """Both hands of a batch in ONE launch: -> (right, left), each what :func:`fit_mano` returns."""
-    dev = _device_of(joints_r, "fit_mano_hands")
-    packs = [_mano_pack(model, "r", dev), _mano_pack(model, "l", dev)]
-    outs = _launch(packs, [joints_r, joints_l], [weights_r, weights_l], [valid_r, valid_l], [init_r, init_l], config, dev)
-    return _result(packs[0], outs[0]), _result(packs[1], outs[1])
+    return _fit(_FIT_JOINTS, "fit_mano_hands", "rl", model, [joints_r, joints_l], [weights_r, weights_l], [valid_r, valid_l],
+                [init_r, init_l], config)
 
 
 def fit_targets(targets, model, meta_info=None, config=None) -> xdict:
@@ -168,17 +216,9 @@ def fit_targets(targets, model, meta_info=None, config=None) -> xdict:
     ``HandsWrapper.process_data`` builds the ground-truth mesh from -- and ``mano.fit.rmse.{r,l}`` (B) and
     ``mano.fit.transl.{r,l}`` (B,3) are added; ``targets`` itself is left as it was.  ``meta_info["right_valid"]`` /
     ``["left_valid"]`` (B, on the device), where present, say which rows are fitted."""
-    dev = _device_of(targets["mano.j3d.full.r"], "fit_targets")
-    flag = lambda k: meta_info[k] if meta_info is not None and k in meta_info else None
-    fits = fit_mano_hands(targets["mano.j3d.full.r"], targets["mano.j3d.full.l"], model, valid_r=flag("right_valid"),
-                          valid_l=flag("left_valid"), config=config)
-    out = xdict(targets)
-    for h, f in zip("rl", fits):
-        out.overwrite(f"mano.pose.{h}", f["pose_aa"])
-        out.overwrite(f"mano.beta.{h}", f["beta"])
-        out.overwrite(f"mano.fit.rmse.{h}", f["rmse"])
-        out.overwrite(f"mano.fit.transl.{h}", f["transl"])
-    return out
+    fits = _fit(_FIT_JOINTS, "fit_targets", "rl", model, [targets["mano.j3d.full.r"], targets["mano.j3d.full.l"]], [None, None],
+                _valid_flags(meta_info), [None, None], config)
+    return _with_fits(targets, fits, _TARGET_KEYS)
 
 
 # ---- fitting to 2-D keypoints ------------------------------------------------------------------------------------------------
@@ -204,14 +244,7 @@ class Fit2DConfig:
     prior_to_init: bool = False
 
     def c_struct(self) -> Fit2DCfg:
-        for name in ("iters_rigid", "iters"):
-            v = getattr(self, name)
-            if int(v) != v or v < 0:
-                raise ValueError(f"hands_amd: {name} is a non-negative integer, got {v!r}")
-        for name in ("lambda_beta", "lambda_pose", "mu0", "robust_sigma"):
-            v = float(getattr(self, name))
-            if not (v >= 0.0 and v != float("inf")):
-                raise ValueError(f"hands_amd: {name} is finite and not negative, got {v!r}")
+        _check_config(self, ("iters_rigid", "iters"), ("lambda_beta", "lambda_pose", "mu0", "robust_sigma"))
         z = float(self.z_min)
         if not (z > 0.0 and z != float("inf")):
             raise ValueError(f"hands_amd: z_min is finite and positive, got {z!r}")
@@ -219,42 +252,9 @@ class Fit2DConfig:
                         float(self.robust_sigma), z, int(bool(self.fit_shape)), int(bool(self.prior_to_init)))
 
 
-_INIT_SHAPES = (("pose", lambda B: (B, 16, 3, 3)), ("beta", lambda B: (B, 10)), ("transl", lambda B: (B, 3)))
-
-
-def _launch2d(packs, kp2d, K, weights, valids, inits, config, dev):
-    """One hands_mano_fit2d_f32 launch over len(packs) sides of B rows; -> per side (pose, beta, transl, rmse, steps, start,
-    j3d, j2d)."""
-    n, B = len(packs), kp2d[0].shape[0]
-    K = _opt(K, (B, 3, 3), dev, "intrinsics")
-    sides, outs, keep = (ManoFit2DSide * n)(), [], [K]
-    for i in range(n):
-        y = _opt(kp2d[i], (B, 21, 2), dev, "kp2d")
-        w, v = _opt(weights[i], (B, 21), dev, "weights"), _opt(valids[i], (B,), dev, "valid")
-        init = (None, None, None)
-        if inits[i] is not None:
-            init = tuple(_opt(a, s(B), dev, "init " + k) for a, (k, s) in zip(inits[i], _INIT_SHAPES))
-            if len(init) != 3 or any(a is None for a in init):
-                raise ValueError("hands_amd: init is (pose (B,16,3,3), beta (B,10), transl (B,3)), all three")
-        o = (torch.empty(B, 16, 3, 3, device=dev), torch.empty(B, 10, device=dev), torch.empty(B, 3, device=dev),
-             torch.empty(B, device=dev), torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
-             torch.empty(B, 21, 3, device=dev), torch.empty(B, 21, 2, device=dev))
-        consts = ManoFitConsts(*[ptr(packs[i][k]) for k in _CONST_KEYS])
-        sides[i] = ManoFit2DSide(consts, ptr(y), ptr(w), ptr(v), ptr(init[0]), ptr(init[1]), ptr(init[2]), *[ptr(t) for t in o])
-        outs.append(o)
-        keep.append((y, w, v, init))           # converted copies stay alive until the launch is queued
-    cfg = (config or Fit2DConfig()).c_struct()
-    check(_lib.lib().hands_mano_fit2d_f32(sides, n, ptr(K), C.byref(cfg), B, torch.cuda.current_stream(dev).cuda_stream),
-          "hands_mano_fit2d_f32")
-    return outs
-
-
-def _result2d(pack, out):
-    """pose, beta, transl, rmse, steps, start, j3d, j2d and pose_aa (B,48), in that order."""
-    r = _result(pack, out[:5])
-    aa = r.pop("pose_aa")
-    r.update(start=out[5], j3d=out[6], j2d=out[7], pose_aa=aa)
-    return r
+_FIT_2D = _Fit("hands_mano_fit2d_f32", ManoFit2DSide, ManoFitConsts, _CONST_KEYS, "kp2d", (21, 2), 21,
+               (("start", (), torch.int32), ("j3d", (21, 3), torch.float32), ("j2d", (21, 2), torch.float32)), Fit2DConfig,
+               (("intrinsics", (3, 3)),))
 
 
 def fit_mano_2d(kp2d, intrinsics, model_or_layer, side="r", weights=None, valid=None, init=None, config=None) -> xdict:
@@ -272,18 +272,14 @@ def fit_mano_2d(kp2d, intrinsics, model_or_layer, side="r", weights=None, valid=
     keypoints, a non-finite weighted keypoint, intrinsic or initial value, K00 <= 0 or K11 <= 0, an initial state with a
     weighted joint at Z <= z_min, no start candidate) has the mean pose, zeros, ``rmse`` NaN, 0 steps, ``start`` -1 and NaN in
     ``j3d`` and ``j2d``."""
-    dev = _device_of(kp2d, "fit_mano_2d")
-    pack = _mano_pack(model_or_layer, side, dev)
-    return _result2d(pack, _launch2d([pack], [kp2d], intrinsics, [weights], [valid], [init], config, dev)[0])
+    return _fit(_FIT_2D, "fit_mano_2d", (side,), model_or_layer, [kp2d], [weights], [valid], [init], config, [intrinsics])[0]
 
 
 def fit_mano_hands_2d(kp2d_r, kp2d_l, intrinsics, model, weights_r=None, weights_l=None, valid_r=None, valid_l=None, init_r=None,
                       init_l=None, config=None):
     """Both hands of a batch in ONE launch, sharing ``intrinsics``: -> (right, left), each what :func:`fit_mano_2d` returns."""
-    dev = _device_of(kp2d_r, "fit_mano_hands_2d")
-    packs = [_mano_pack(model, "r", dev), _mano_pack(model, "l", dev)]
-    outs = _launch2d(packs, [kp2d_r, kp2d_l], intrinsics, [weights_r, weights_l], [valid_r, valid_l], [init_r, init_l], config, dev)
-    return _result2d(packs[0], outs[0]), _result2d(packs[1], outs[1])
+    return _fit(_FIT_2D, "fit_mano_hands_2d", "rl", model, [kp2d_r, kp2d_l], [weights_r, weights_l], [valid_r, valid_l],
+                [init_r, init_l], config, [intrinsics])
 
 
 def _unnormalize(t, img_res):
@@ -302,20 +298,13 @@ def fit_targets_2d(targets, model, meta_info, weights_r=None, weights_l=None, co
     ``j3d``) are the fit, and ``mano.fit.rmse_px.{r,l}`` (B) and ``mano.fit.transl.{r,l}`` (B,3) are added; ``targets`` itself
     is left as it was.  ``meta_info["right_valid"]`` / ``["left_valid"]``, where present, say which rows are fitted.  The 3-D
     entries reproduce the keypoints, not the depth or scale of the true hand."""
-    dev = _device_of(targets["mano.j2d.norm.r"], "fit_targets_2d")
-    flag = lambda k: meta_info[k] if k in meta_info else None
+    (config or Fit2DConfig()).c_struct()
+    _device_of(targets["mano.j2d.norm.r"], "fit_targets_2d")
     res = float(getattr(model, "img_res", 224))
-    fits = fit_mano_hands_2d(_unnormalize(targets["mano.j2d.norm.r"], res), _unnormalize(targets["mano.j2d.norm.l"], res),
-                             meta_info["intrinsics"], model, weights_r=weights_r, weights_l=weights_l,
-                             valid_r=flag("right_valid"), valid_l=flag("left_valid"), config=config)
-    out = xdict(targets)
-    for h, f in zip("rl", fits):
-        out.overwrite(f"mano.pose.{h}", f["pose_aa"])
-        out.overwrite(f"mano.beta.{h}", f["beta"])
-        out.overwrite(f"mano.j3d.full.{h}", f["j3d"])
-        out.overwrite(f"mano.fit.rmse_px.{h}", f["rmse"])
-        out.overwrite(f"mano.fit.transl.{h}", f["transl"])
-    return out
+    fits = _fit(_FIT_2D, "fit_targets_2d", "rl", model, [_unnormalize(targets[f"mano.j2d.norm.{h}"], res) for h in "rl"],
+                [weights_r, weights_l], _valid_flags(meta_info), [None, None], config, [meta_info["intrinsics"]])
+    return _with_fits(targets, fits, (("mano.pose", "pose_aa"), ("mano.beta", "beta"), ("mano.j3d.full", "j3d"),
+                                      ("mano.fit.rmse_px", "rmse"), ("mano.fit.transl", "transl")))
 
 
 _HEAD_KEYS = ("cam_t.wp", "cam_t", "joints3d", "vertices", "j3d.cam", "v3d.cam", "j2d.norm", "beta", "pose")
@@ -354,9 +343,7 @@ def refine_predictions(pred, kp2d_r, kp2d_l, model, meta_info, weights_r=None, w
     B = pred["mano.pose.r"].shape[0]
     inits = []
     for h in "rl":
-        pose = f32(pred[f"mano.pose.{h}"])
-        aa = torch.empty(B, 48, device=dev)
-        check(L.hands_matrix_to_axis_angle_f32(ptr(pose), ptr(aa), B * 16, stream), "matrix_to_axis_angle")
+        aa = _matrix_to_aa(f32(pred[f"mano.pose.{h}"]))
         inits.append((_aa_to_matrix(aa + P[f"mano_{h}"]["pose_mean"]), f32(pred[f"mano.beta.{h}"]), f32(pred[f"mano.cam_t.{h}"])))
     config = config or Fit2DConfig(iters_rigid=0, prior_to_init=True)
     fits = fit_mano_hands_2d(kp2d_r, kp2d_l, K, model, weights_r, weights_l, valid_r, valid_l, inits[0], inits[1], config)
@@ -390,36 +377,8 @@ def refine_predictions(pred, kp2d_r, kp2d_l, model, meta_info, weights_r=None, w
 _VERTS_CONST_KEYS = ("pose_mean", "J_template", "J_shapedirs", "v_template", "shapedirs", "lbs_weights", "posedirs_vm")
 
 
-def _launch_verts(packs, verts, weights, valids, inits, config, dev):
-    """One hands_mano_fit_verts_f32 launch over len(packs) sides of B rows; -> per side (pose, beta, transl, rmse, steps, j3d)."""
-    n, B = len(packs), verts[0].shape[0]
-    sides, outs, keep = (ManoFitVertsSide * n)(), [], []
-    for i in range(n):
-        y = _opt(verts[i], (B, 778, 3), dev, "verts")
-        w, v = _opt(weights[i], (B, 778), dev, "weights"), _opt(valids[i], (B,), dev, "valid")
-        init = (None, None, None)
-        if inits[i] is not None:
-            init = tuple(_opt(a, s(B), dev, "init " + k) for a, (k, s) in zip(inits[i], _INIT_SHAPES))
-            if len(init) != 3 or any(a is None for a in init):
-                raise ValueError("hands_amd: init is (pose (B,16,3,3), beta (B,10), transl (B,3)), all three")
-        o = (torch.empty(B, 16, 3, 3, device=dev), torch.empty(B, 10, device=dev), torch.empty(B, 3, device=dev),
-             torch.empty(B, device=dev), torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, 21, 3, device=dev))
-        consts = ManoFitVertsConsts(*[ptr(packs[i][k]) for k in _VERTS_CONST_KEYS])
-        sides[i] = ManoFitVertsSide(consts, ptr(y), ptr(w), ptr(v), ptr(init[0]), ptr(init[1]), ptr(init[2]), *[ptr(t) for t in o])
-        outs.append(o)
-        keep.append((y, w, v, init))           # converted copies stay alive until the launch is queued
-    cfg = (config or FitConfig()).c_struct()
-    check(_lib.lib().hands_mano_fit_verts_f32(sides, n, C.byref(cfg), B, torch.cuda.current_stream(dev).cuda_stream),
-          "hands_mano_fit_verts_f32")
-    return outs
-
-
-def _result_verts(pack, out):
-    """pose, beta, transl, rmse, steps, j3d and pose_aa (B,48), in that order."""
-    r = _result(pack, out[:5])
-    aa = r.pop("pose_aa")
-    r.update(j3d=out[5], pose_aa=aa)
-    return r
+_FIT_VERTS = _Fit("hands_mano_fit_verts_f32", ManoFitVertsSide, ManoFitVertsConsts, _VERTS_CONST_KEYS, "verts", (778, 3), 778,
+                  (("j3d", (21, 3), torch.float32),), FitConfig)
 
 
 def fit_mano_verts(verts, model_or_layer, side="r", weights=None, valid=None, init=None, config=None) -> xdict:
@@ -435,20 +394,14 @@ def fit_mano_verts(verts, model_or_layer, side="r", weights=None, valid=None, in
     the mesh is a MANO mesh, recovers pose and shape; it does not register a surface or a point cloud without correspondences
     and fits no scale.  A row that is not fitted (``valid`` 0, fewer than four weighted vertices, a non-finite weighted vertex
     or initial value) has the mean pose, zeros, ``rmse`` NaN, 0 steps and NaN in ``j3d``."""
-    (config or FitConfig()).c_struct()             # a bad configuration is refused before anything else is looked at
-    dev = _device_of(verts, "fit_mano_verts")
-    pack = _mano_pack(model_or_layer, side, dev)
-    return _result_verts(pack, _launch_verts([pack], [verts], [weights], [valid], [init], config, dev)[0])
+    return _fit(_FIT_VERTS, "fit_mano_verts", (side,), model_or_layer, [verts], [weights], [valid], [init], config)[0]
 
 
 def fit_mano_hands_verts(verts_r, verts_l, model, weights_r=None, weights_l=None, valid_r=None, valid_l=None, init_r=None,
                          init_l=None, config=None):
     """Both hands of a batch in ONE launch: -> (right, left), each what :func:`fit_mano_verts` returns."""
-    (config or FitConfig()).c_struct()
-    dev = _device_of(verts_r, "fit_mano_hands_verts")
-    packs = [_mano_pack(model, "r", dev), _mano_pack(model, "l", dev)]
-    outs = _launch_verts(packs, [verts_r, verts_l], [weights_r, weights_l], [valid_r, valid_l], [init_r, init_l], config, dev)
-    return _result_verts(packs[0], outs[0]), _result_verts(packs[1], outs[1])
+    return _fit(_FIT_VERTS, "fit_mano_hands_verts", "rl", model, [verts_r, verts_l], [weights_r, weights_l], [valid_r, valid_l],
+                [init_r, init_l], config)
 
 
 def fit_targets_verts(targets, model, meta_info=None, config=None) -> xdict:
@@ -458,17 +411,6 @@ def fit_targets_verts(targets, model, meta_info=None, config=None) -> xdict:
     (B) and ``mano.fit.transl.{r,l}`` (B,3) are added, and ``mano.j3d.full.{r,l}`` is the fit's ``j3d`` where ``targets`` has no
     such key (a present one is left alone); ``targets`` itself is left as it was.  ``meta_info["right_valid"]`` /
     ``["left_valid"]`` (B, on the device), where present, say which rows are fitted."""
-    (config or FitConfig()).c_struct()
-    dev = _device_of(targets["mano.v3d.full.r"], "fit_targets_verts")
-    flag = lambda k: meta_info[k] if meta_info is not None and k in meta_info else None
-    fits = fit_mano_hands_verts(targets["mano.v3d.full.r"], targets["mano.v3d.full.l"], model, valid_r=flag("right_valid"),
-                                valid_l=flag("left_valid"), config=config)
-    out = xdict(targets)
-    for h, f in zip("rl", fits):
-        out.overwrite(f"mano.pose.{h}", f["pose_aa"])
-        out.overwrite(f"mano.beta.{h}", f["beta"])
-        out.overwrite(f"mano.fit.rmse.{h}", f["rmse"])
-        out.overwrite(f"mano.fit.transl.{h}", f["transl"])
-        if f"mano.j3d.full.{h}" not in targets:
-            out.overwrite(f"mano.j3d.full.{h}", f["j3d"])
-    return out
+    fits = _fit(_FIT_VERTS, "fit_targets_verts", "rl", model, [targets["mano.v3d.full.r"], targets["mano.v3d.full.l"]],
+                [None, None], _valid_flags(meta_info), [None, None], config)
+    return _with_fits(targets, fits, _TARGET_KEYS + (("mano.j3d.full", "j3d"),), keep=("mano.j3d.full",))

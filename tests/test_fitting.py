@@ -173,3 +173,29 @@ def test_fitting_refuses_cpu_tensors():
         hands_amd.fit_mano(torch.zeros(1, 21, 3), None)
     with pytest.raises(RuntimeError, match="HIP device only"):
         hands_amd.fit_targets({"mano.j3d.full.r": torch.zeros(1, 21, 3), "mano.j3d.full.l": torch.zeros(1, 21, 3)}, None)
+
+
+def test_the_three_fits_share_the_config_and_init_rules(monkeypatch):
+    """One launch path: the joint and the 2-D fit refuse a bad configuration before they look at a tensor, as the vertex fit
+    does (tests/test_fit_verts.py), and every fit refuses an ``init`` that is not three tensors with the same ValueError."""
+    from hands_amd import Fit2DConfig, fitting
+    y3, y2, K = torch.zeros(1, 21, 3), torch.zeros(1, 21, 2), torch.eye(3)[None]
+    for bad in (dict(iters=-1), dict(lambda_pose=float("nan")), dict(mu0=float("inf"))):
+        with pytest.raises(ValueError):
+            hands_amd.fit_mano(y3, None, config=FitConfig(**bad))
+        with pytest.raises(ValueError):
+            hands_amd.fit_mano_hands(y3, y3, None, config=FitConfig(**bad))
+        with pytest.raises(ValueError):
+            hands_amd.fit_targets({"mano.j3d.full.r": y3, "mano.j3d.full.l": y3}, None, config=FitConfig(**bad))
+        with pytest.raises(ValueError):
+            hands_amd.fit_mano_2d(y2, K, None, config=Fit2DConfig(**bad))
+        with pytest.raises(ValueError):
+            hands_amd.fit_mano_hands_2d(y2, y2, K, None, config=Fit2DConfig(**bad))
+        with pytest.raises(ValueError):
+            hands_amd.fit_targets_2d({"mano.j2d.norm.r": y2, "mano.j2d.norm.l": y2}, None, {"intrinsics": K}, config=Fit2DConfig(**bad))
+    monkeypatch.setattr(fitting, "_opt", lambda v, *a: v)                 # the device rule comes first on this machine
+    a = torch.zeros(1)
+    for fit, shared in ((fitting._FIT_JOINTS, ()), (fitting._FIT_2D, (K,)), (fitting._FIT_VERTS, ())):
+        for init in ((a, a), (a, a, a, a), (a, None, a)):
+            with pytest.raises(ValueError, match=r"init is \(pose"):
+                fitting._launch(fit, [None], [a], [None], [None], [init], None, "cpu", shared)
