@@ -23,7 +23,9 @@ from .penetration import (seal_mesh, apply_seal, signed_distance_to_mesh, interh
 from .temporal import accel_error, evaluate_accel_metrics, AccelMetrics  # noqa: F401
 from .smoothing import SmoothConfig, smooth_mano_params, smooth_predictions, TemporalSmoother  # noqa: F401
 from .fitting import (FitConfig, fit_mano, fit_mano_hands, fit_targets, Fit2DConfig, fit_mano_2d, fit_mano_hands_2d,  # noqa: F401
-                      fit_targets_2d, refine_predictions, fit_mano_verts, fit_mano_hands_verts, fit_targets_verts)
+                      fit_targets_2d, refine_predictions, fit_mano_verts, fit_mano_hands_verts, fit_targets_verts,
+                      SurfaceFitConfig, fit_mano_surface, fit_mano_hands_surface, correspond_on_mesh, RegisterConfig,
+                      register_mano, register_mano_hands, register_predictions)
 
 __all__ = ["HandsLight", "DEFAULT_ARGS", "ManoHeadsPlan", "HAMER", "HAMER_DEFAULT_ARGS", "HandOccNet", "HANDOCC_DEFAULT_ARGS", "xdict", "prefix_dict", "ManoAsset", "synthetic_mano_asset",
            "build_mano_asset", "apply_recipe", "synthetic_inputs", "HandsFrontEnd", "GraphedForward", "HandsWrapper",
@@ -35,4 +37,6 @@ __all__ = ["HandsLight", "DEFAULT_ARGS", "ManoHeadsPlan", "HAMER", "HAMER_DEFAUL
            "SmoothConfig", "smooth_mano_params", "smooth_predictions", "TemporalSmoother",
            "FitConfig", "fit_mano", "fit_mano_hands", "fit_targets",
            "Fit2DConfig", "fit_mano_2d", "fit_mano_hands_2d", "fit_targets_2d", "refine_predictions",
-           "fit_mano_verts", "fit_mano_hands_verts", "fit_targets_verts"]
+           "fit_mano_verts", "fit_mano_hands_verts", "fit_targets_verts", "SurfaceFitConfig", "fit_mano_surface",
+           "fit_mano_hands_surface", "correspond_on_mesh", "RegisterConfig", "register_mano", "register_mano_hands",
+           "register_predictions"]

@@ -150,6 +150,26 @@ class ManoFitVertsSide(C.Structure):
         "verts", "weights", "valid", "init_pose", "init_beta", "init_transl", "pose", "beta", "transl", "rmse", "steps", "j3d")]
 
 
+class ManoFitSurfConsts(C.Structure):
+    """hands_mano_fit_surf_consts (include/hands_hip.h): hands_mano_fit_verts_consts and the face list (1538,3) int32."""
+    _fields_ = [(n, C.c_void_p) for n in ("pose_mean", "J_template", "J_shapedirs", "v_template", "shapedirs", "lbs_weights",
+                                          "posedirs_vm", "faces")]
+
+
+class ManoFitSurfSide(C.Structure):
+    """hands_mano_fit_surf_side (include/hands_hip.h): one hand of a hands_mano_fit_surf_f32 call; weights, valid, init_* and
+    normals may be NULL."""
+    _fields_ = [("consts", ManoFitSurfConsts)] + [(n, C.c_void_p) for n in (
+        "points", "weights", "valid", "init_pose", "init_beta", "init_transl", "pose", "beta", "transl", "rmse", "steps", "j3d",
+        "verts", "face_idx", "bary", "normals")]
+
+
+class FitSurfCfg(C.Structure):
+    """hands_fit_surf_cfg (include/hands_hip.h)."""
+    _fields_ = [("iters", C.c_int), ("lambda_beta", C.c_double), ("lambda_pose", C.c_double), ("mu0", C.c_double),
+                ("tangent_weight", C.c_double)]
+
+
 class LossIn(C.Structure):
     """hands_loss_in (include/hands_hip.h): the first LOSS_N_MANDATORY pointers are mandatory, the rest come in groups."""
     _fields_ = [(n, C.c_void_p) for n in (
@@ -267,6 +287,8 @@ SIGNATURES = {
     "hands_mano_fit_f32": [C.POINTER(ManoFitSide), _I, C.POINTER(FitCfg), _I, _P],
     "hands_mano_fit2d_f32": [C.POINTER(ManoFit2DSide), _I, _P, C.POINTER(Fit2DCfg), _I, _P],
     "hands_mano_fit_verts_f32": [C.POINTER(ManoFitVertsSide), _I, C.POINTER(FitCfg), _I, _P],
+    "hands_mano_fit_surf_f32": [C.POINTER(ManoFitSurfSide), _I, C.POINTER(FitSurfCfg), _I, _I, _P],
+    "hands_mesh_correspond_f32": [_P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "hands_loss_light_f32": [C.POINTER(LossIn), _I, _I, _I, _P, _P, _P, _P, _P],
     "hands_mano_pose_aa_f32": [C.POINTER(ManoConsts), _P, _P, _I, _P, _I, _P, _P, _I, _P],
     "hands_gt_targets_f32": [_P, _P, _P, _P, _F, _P, _P, _P, _I, _I, _P],

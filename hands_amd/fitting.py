@@ -17,8 +17,14 @@ The ``*_verts`` functions fit the same unknowns to the 778 vertices of a mesh in
 csrc/fit_verts.hip; DESIGN.md section 7 "MANO fitting to 778 vertices", tests/fit_verts_ref.py): for mesh-only annotations
 (``fit_targets_verts``, ``HandsWrapper.fit_gt_verts``) and for turning any MANO-topology mesh into ``mano.pose`` /
 ``mano.beta``.  That fit reproduces the VERTICES: where the mesh is a MANO mesh it recovers pose and shape.  It does no
-correspondence-free registration (no ICP to a surface or a point cloud: vertex n of the target is vertex n of the model) and
-fits no scale.
+correspondence-free registration (vertex n of the target is vertex n of the model) and fits no scale.
+
+``fit_mano_surface`` fits the same unknowns to P points whose places ON the model's surface are named: row k is a face of the
+asset's face list and three coefficients (hands_mano_fit_surf_f32, csrc/fit_surf.hip; DESIGN.md section 7 "MANO fitting to
+surface correspondences and ICP registration", tests/fit_surf_ref.py) -- mocap markers at known places, or the correspondences
+of one ICP round.  ``correspond_on_mesh`` (hands_mesh_correspond_f32) derives such rows from a point cloud and a posed mesh, and
+``register_mano`` alternates the two: data-to-model ICP from a caller's initial state.  That loop lowers the cloud's distance
+to the surface; it is local, fits no scale, and observes no twist of a round finger.
 """
 from __future__ import annotations
 
@@ -29,8 +35,9 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from ._lib import (Fit2DCfg, FitCfg, ManoFit2DSide, ManoFitConsts, ManoFitSide, ManoFitVertsConsts, ManoFitVertsSide, check,
-                   ptr)
+from ._lib import (Fit2DCfg, FitCfg, FitSurfCfg, ManoFit2DSide, ManoFitConsts, ManoFitSide, ManoFitSurfConsts, ManoFitSurfSide,
+                   ManoFitVertsConsts, ManoFitVertsSide, check, ptr)
+from .metrics import faces_on_device
 from .packing import pack_mano
 from .xdict import xdict
 
@@ -97,37 +104,48 @@ def _mano_pack(model_or_layer, side, dev):
     return kept[1]
 
 
-def _opt(v, shape, dev, what):
-    """An optional input as a contiguous fp32 tensor: it has to be on the device already (nothing here copies from the host)."""
+def _opt(v, shape, dev, what, dtype=torch.float32):
+    """An optional input as a contiguous fp32 (or ``dtype``) tensor: it has to be on the device already (nothing here copies
+    from the host)."""
     if v is None:
         return None
     if _device_of(v, f"fit_mano ({what})") != dev:
         raise RuntimeError(f"hands_amd: {what} is on {v.device}, the joints on {dev}")
-    v = v.to(dtype=torch.float32).contiguous()
+    v = v.to(dtype=dtype).contiguous()
     if tuple(v.shape) != shape:
         raise ValueError(f"hands_amd: {what} has shape {shape}, got {tuple(v.shape)}")
     return v
 
 
-_Fit = namedtuple("_Fit", "entry side consts const_keys data data_shape n_weights extras config shared", defaults=((),))
+_Fit = namedtuple("_Fit", "entry side consts const_keys data data_shape n_weights extras config shared more", defaults=((), ()))
 """What tells one fit from another on the way to its C entry: the entry's name, the ctypes side and consts structs, the keys of
 the pack the consts are, name and per-row shape of the data tensor, the number of weights of a row, the outputs behind pose,
-beta, transl, rmse and steps as (name, per-row shape, dtype), the configuration class, and the tensors the entry takes once for
-all sides as (name, per-row shape)."""
+beta, transl, rmse and steps as (name, per-row shape, dtype), the configuration class, the tensors the entry takes once for
+all sides as (name, per-row shape), and the data tensors a side takes beside the first, behind its outputs, as (name, per-row
+shape, dtype, required).  ``n_weights`` -1: the rows of a hand are as many as the data tensor has (a -1 in a shape stands for
+that number), and the entry takes the number behind B."""
 
 _OUTPUTS = (("pose", (16, 3, 3), torch.float32), ("beta", (10,), torch.float32), ("transl", (3,), torch.float32),
             ("rmse", (), torch.float32), ("steps", (), torch.int32))
 _FIT_JOINTS = _Fit("hands_mano_fit_f32", ManoFitSide, ManoFitConsts, _CONST_KEYS, "joints", (21, 3), 21, (), FitConfig)
 
 
-def _launch(fit, packs, data, weights, valids, inits, cfg, dev, shared=()):
+def _launch(fit, packs, data, weights, valids, inits, cfg, dev, shared=(), more=None):
     """One launch of ``fit.entry`` over len(packs) sides of B rows; -> per side the outputs, _OUTPUTS then ``fit.extras``."""
     n, B = len(packs), data[0].shape[0]
+    rows = fit.n_weights if fit.n_weights >= 0 else (int(data[0].shape[1]) if data[0].dim() > 1 else 0)
+    dims = lambda s: tuple(rows if d < 0 else d for d in s)
+    if fit.n_weights < 0 and not 1 <= rows <= MAX_SURFACE_ROWS:
+        raise ValueError(f"hands_amd: {fit.data} has 1 to {MAX_SURFACE_ROWS} rows per hand, got {rows}")
     shared = [_opt(t, (B,) + s, dev, k) for t, (k, s) in zip(shared, fit.shared)]
     sides, outs, keep = (fit.side * n)(), [], []
     for i in range(n):
-        y = _opt(data[i], (B,) + fit.data_shape, dev, fit.data)
-        w, v = _opt(weights[i], (B, fit.n_weights), dev, "weights"), _opt(valids[i], (B,), dev, "valid")
+        y = _opt(data[i], (B,) + dims(fit.data_shape), dev, fit.data)
+        w, v = _opt(weights[i], (B, rows), dev, "weights"), _opt(valids[i], (B,), dev, "valid")
+        extra = [_opt(t, (B,) + dims(s), dev, k, dt) for t, (k, s, dt, _) in zip(more[i] if more else (), fit.more)]
+        for t, (k, _, _, required) in zip(extra, fit.more):
+            if required and t is None:
+                raise ValueError(f"hands_amd: {k} is required")
         init = (None, None, None)
         if inits[i] is not None:
             if len(inits[i]) == 3:
@@ -136,10 +154,10 @@ def _launch(fit, packs, data, weights, valids, inits, cfg, dev, shared=()):
                 raise ValueError("hands_amd: init is (pose (B,16,3,3), beta (B,10), transl (B,3)), all three")
         o = [torch.empty((B,) + s, dtype=t, device=dev) for _, s, t in _OUTPUTS + fit.extras]
         consts = fit.consts(*[ptr(packs[i][k]) for k in fit.const_keys])
-        sides[i] = fit.side(consts, ptr(y), ptr(w), ptr(v), *[ptr(t) for t in init], *[ptr(t) for t in o])
+        sides[i] = fit.side(consts, ptr(y), ptr(w), ptr(v), *[ptr(t) for t in init], *[ptr(t) for t in o], *[ptr(t) for t in extra])
         outs.append(o)
-        keep.append((y, w, v, init))           # converted copies stay alive until the launch is queued
-    check(getattr(_lib.lib(), fit.entry)(sides, n, *[ptr(t) for t in shared], C.byref(cfg), B,
+        keep.append((y, w, v, init, extra))    # converted copies stay alive until the launch is queued
+    check(getattr(_lib.lib(), fit.entry)(sides, n, *[ptr(t) for t in shared], C.byref(cfg), B, *([rows] if fit.n_weights < 0 else []),
                                          torch.cuda.current_stream(dev).cuda_stream), fit.entry)
     return outs
 
@@ -160,12 +178,12 @@ def _result(fit, pack, out):
     return r
 
 
-def _fit(fit, what, hands, model_or_layer, data, weights, valids, inits, config, shared=()):
+def _fit(fit, what, hands, model_or_layer, data, weights, valids, inits, config, shared=(), more=None):
     """The fit of the sides ``hands`` (("r",), ("l",) or "rl") in one launch; -> per side what the public functions return."""
     cfg = (config or fit.config()).c_struct()      # a bad configuration is refused before anything else is looked at
     dev = _device_of(data[0], what)
     packs = [_mano_pack(model_or_layer, h, dev) for h in hands]
-    outs = _launch(fit, packs, data, weights, valids, inits, cfg, dev, shared)
+    outs = _launch(fit, packs, data, weights, valids, inits, cfg, dev, shared, more)
     return tuple(_result(fit, p, o) for p, o in zip(packs, outs))
 
 
@@ -334,19 +352,33 @@ def refine_predictions(pred, kp2d_r, kp2d_l, model, meta_info, weights_r=None, w
     the head clamps the weak-perspective scale at 0.1, so a depth beyond 2 f / (0.1 img_res) -- 89 m at f = 1000, img_res = 224
     -- is not refined.  The translation goes through the head's fp32 camera conversion, so the refined ``mano.cam_t`` is the
     fitted one to fp32 rounding of its depth."""
-    from .mano_head import run_mano_heads
     dev = _device_of(pred["mano.pose.r"], "refine_predictions")
-    L, stream = _lib.lib(), torch.cuda.current_stream(dev).cuda_stream
     P = model.packed(dev)
+    K = meta_info["intrinsics"].to(device=dev, dtype=torch.float32).contiguous()
+    inits = _prediction_state(pred, P, dev)
+    config = config or Fit2DConfig(iters_rigid=0, prior_to_init=True)
+    fits = fit_mano_hands_2d(kp2d_r, kp2d_l, K, model, weights_r, weights_l, valid_r, valid_l, inits[0], inits[1], config)
+    return _with_refits(pred, fits, model, P, K, dev)
+
+
+def _prediction_state(pred, P, dev):
+    """Per hand the state a prediction is: (Exp(Log(mano.pose_j) + hands_mean_j), mano.beta, mano.cam_t), fp32 on ``dev``."""
     f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()
-    K = f32(meta_info["intrinsics"])
-    B = pred["mano.pose.r"].shape[0]
     inits = []
     for h in "rl":
         aa = _matrix_to_aa(f32(pred[f"mano.pose.{h}"]))
         inits.append((_aa_to_matrix(aa + P[f"mano_{h}"]["pose_mean"]), f32(pred[f"mano.beta.{h}"]), f32(pred[f"mano.cam_t.{h}"])))
-    config = config or Fit2DConfig(iters_rigid=0, prior_to_init=True)
-    fits = fit_mano_hands_2d(kp2d_r, kp2d_l, K, model, weights_r, weights_l, valid_r, valid_l, inits[0], inits[1], config)
+    return inits
+
+
+def _with_refits(pred, fits, model, P, K, dev):
+    """What ``refine_predictions`` and ``register_predictions`` do after their fit: the nine MANO-head keys per hand recomputed by
+    one ``hands_mano_heads_f32`` launch from the fitted state, on the rows that were fitted and whose depth the head's
+    weak-perspective camera can represent; every other key and row of ``pred`` handed through; ``refined.{r,l}`` added."""
+    from .mano_head import run_mano_heads
+    L, stream = _lib.lib(), torch.cuda.current_stream(dev).cuda_stream
+    f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()
+    B = pred["mano.pose.r"].shape[0]
     res = float(getattr(model, "img_res", 224))
     focal = 0.5 * (K[:, 0, 0] + K[:, 1, 1])
     rot, shape, cam = torch.empty(2 * B, 16, 3, 3, device=dev), torch.empty(2 * B, 10, device=dev), torch.empty(2 * B, 3, device=dev)
@@ -414,3 +446,194 @@ def fit_targets_verts(targets, model, meta_info=None, config=None) -> xdict:
     fits = _fit(_FIT_VERTS, "fit_targets_verts", "rl", model, [targets["mano.v3d.full.r"], targets["mano.v3d.full.l"]],
                 [None, None], _valid_flags(meta_info), [None, None], config)
     return _with_fits(targets, fits, _TARGET_KEYS + (("mano.j3d.full", "j3d"),), keep=("mano.j3d.full",))
+
+
+# ---- fitting to surface correspondences; ICP registration -----------------------------------------------------------------------
+MAX_SURFACE_ROWS = 16384     # HANDS_FIT_SURF_MAX_P of include/hands_hip.h: it bounds time, not memory
+
+
+@dataclass(frozen=True)
+class SurfaceFitConfig:
+    """The four numbers of :class:`FitConfig` and ``tangent_weight`` in [0, 1]: with ``normals``, the part of a residual along
+    the normal counts fully and the part across it ``tangent_weight`` times (point-to-plane at 0, point-to-point at 1, where
+    the normals are not read).  The defaults are UNTUNED starting values, as FitConfig's are."""
+    iters: int = 30
+    lambda_beta: float = 1e-6
+    lambda_pose: float = 1e-6
+    mu0: float = 1e-3
+    tangent_weight: float = 1.0
+
+    def c_struct(self) -> FitSurfCfg:
+        _check_config(self, ("iters",), ("lambda_beta", "lambda_pose", "mu0"))
+        tau = float(self.tangent_weight)
+        if not 0.0 <= tau <= 1.0:
+            raise ValueError(f"hands_amd: tangent_weight is in [0, 1], got {tau!r}")
+        return FitSurfCfg(int(self.iters), float(self.lambda_beta), float(self.lambda_pose), float(self.mu0), tau)
+
+
+_FIT_SURF = _Fit("hands_mano_fit_surf_f32", ManoFitSurfSide, ManoFitSurfConsts, _VERTS_CONST_KEYS + ("faces_i32",), "points", (-1, 3),
+                 -1, (("j3d", (21, 3), torch.float32), ("verts", (778, 3), torch.float32)), SurfaceFitConfig, (),
+                 (("face_idx", (-1,), torch.int32, True), ("bary", (-1, 3), torch.float32, True),
+                  ("normals", (-1, 3), torch.float32, False)))
+
+
+def fit_mano_surface(points, face_idx, bary, model_or_layer, side="r", weights=None, normals=None, valid=None, init=None,
+                     config=None) -> xdict:
+    """Fit ONE hand of a batch to points whose places on the model's surface are known: ``points`` (B,P,3) in metres, row k
+    belonging to face ``face_idx`` (B,P) of the asset's face list (0..1537) at the coefficients ``bary`` (B,P,3), finite, neither
+    clamped nor normalised: the model's point is sum_i bary_i * vertex faces[face_idx][i].  P is 1 to 16384, the same for the
+    batch.  Every tensor is on the device (RuntimeError otherwise).  ``weights`` (B,P) >= 0 (default 1; a row of weight 0 is
+    never read -- its point, coefficients and normal may be NaN, its face -1: that is how hands with fewer rows are padded),
+    ``normals`` (B,P,3) with ``config.tangent_weight`` < 1 weigh a residual's part across the normal down (a zero normal: no
+    such weighting for the row), ``valid`` (B), ``init`` (pose, beta, transl) instead of the rest hand aligned rigidly to the
+    points, ``config`` a :class:`SurfaceFitConfig` (untuned defaults).
+
+    Returns an xdict: ``pose``, ``beta``, ``transl``, ``rmse`` (B) -- always the Euclidean sqrt(sum w |c + t - y|^2 / sum w),
+    without the normals' weighting and the priors --, ``steps``, ``j3d`` (B,21,3), ``verts`` (B,778,3) = the fitted vertices +
+    transl, and ``pose_aa`` (B,48).  A hand that is not fitted (``valid`` 0, fewer than four weighted rows, a weighted row with a
+    non-finite value, a weight of +inf or a face outside 0..1537, a non-finite initial value) has the mean pose, zeros, ``rmse``
+    NaN, 0 steps and NaN in ``j3d`` and ``verts``."""
+    return _fit(_FIT_SURF, "fit_mano_surface", (side,), model_or_layer, [points], [weights], [valid], [init], config,
+                more=[(face_idx, bary, normals)])[0]
+
+
+def fit_mano_hands_surface(points_r, face_idx_r, bary_r, points_l, face_idx_l, bary_l, model, weights_r=None, weights_l=None,
+                           normals_r=None, normals_l=None, valid_r=None, valid_l=None, init_r=None, init_l=None, config=None):
+    """Both hands of a batch in ONE launch (the same P for both): -> (right, left), each what :func:`fit_mano_surface` returns."""
+    return _fit(_FIT_SURF, "fit_mano_hands_surface", "rl", model, [points_r, points_l], [weights_r, weights_l], [valid_r, valid_l],
+                [init_r, init_l], config, more=[(face_idx_r, bary_r, normals_r), (face_idx_l, bary_l, normals_l)])
+
+
+def correspond_on_mesh(points, verts, faces, weights=None, max_dist=0.0) -> xdict:
+    """Per query point the closest point of a triangle mesh with what a fit needs, one launch of hands_mesh_correspond_f32:
+    ``points`` (B,P,3), ``verts`` (B,V,3) with V <= 1024, ``faces`` (F,3) integers shared by the batch (F <= 4096), ``weights``
+    (B,P) or None (all 1), on the device.  Returns an xdict of new tensors: ``dist`` (B,P), ``face_idx`` (B,P) int32 and
+    ``closest`` (B,P,3) -- the bits ``closest_on_mesh`` gives --, ``bary`` (B,P,3) the coefficients of ``closest`` on its face,
+    ``normal`` (B,P,3) that face's unit normal (zero for a face without one) and ``weights`` (B,P): the input weight where
+    ``max_dist`` <= 0 or ``dist`` <= ``max_dist``, else 0.  A query of weight 0 is not read: NaN / -1 / NaN / NaN / 0 / 0."""
+    dev = _device_of(points, "correspond_on_mesh")
+    max_dist = float(max_dist)
+    if max_dist != max_dist:
+        raise ValueError("hands_amd: max_dist is a number")
+    points = _opt(points, tuple(points.shape), dev, "points")
+    if points.dim() != 3 or points.shape[2] != 3 or not isinstance(verts, torch.Tensor) or verts.dim() != 3:
+        raise ValueError("hands_amd: points is (B,P,3) and verts (B,V,3)")
+    B, P = points.shape[:2]
+    verts = _opt(verts, (B, verts.shape[1], 3), dev, "verts")
+    w = _opt(weights, (B, P), dev, "weights")
+    fc = faces_on_device(faces, dev)
+    out = xdict(dict(dist=torch.empty(B, P, device=dev), face_idx=torch.empty(B, P, dtype=torch.int32, device=dev),
+                     closest=torch.empty(B, P, 3, device=dev), bary=torch.empty(B, P, 3, device=dev),
+                     normal=torch.empty(B, P, 3, device=dev), weights=torch.empty(B, P, device=dev)))
+    check(_lib.lib().hands_mesh_correspond_f32(ptr(points), ptr(verts), ptr(fc) or None, None, ptr(w), max_dist, *[ptr(t) for t in out.values()],
+                                               B, P, verts.shape[1], fc.shape[0], torch.cuda.current_stream(dev).cuda_stream),
+          "hands_mesh_correspond_f32")
+    return out
+
+
+@dataclass(frozen=True)
+class RegisterConfig:
+    """``rounds`` ICP rounds of ``iters`` Levenberg-Marquardt iterations each (the damping restarts at ``mu0`` every round), the
+    priors' weights, ``tangent_weight`` of the rounds' fits (the normals are those of the closest faces) and ``max_dist`` in
+    metres: a point farther than that from the current surface has weight 0 in its round (<= 0: no such trim).
+
+    The defaults (10, 3, 1e-6, 1e-6, 1e-3, 0.1, 0) are UNTUNED starting points, not tuned on data; DESIGN.md section 7 records
+    what the fp64 restatement reaches with them on a synthetic tube hand."""
+    rounds: int = 10
+    iters: int = 3
+    lambda_beta: float = 1e-6
+    lambda_pose: float = 1e-6
+    mu0: float = 1e-3
+    tangent_weight: float = 0.1
+    max_dist: float = 0.0
+
+    def fit_config(self, iters=None) -> SurfaceFitConfig:
+        """The configuration of a round's fit, checked; ValueError for a bad field."""
+        _check_config(self, ("rounds",), ())
+        if float(self.max_dist) != float(self.max_dist):
+            raise ValueError("hands_amd: max_dist is a number")
+        cfg = SurfaceFitConfig(self.iters if iters is None else iters, self.lambda_beta, self.lambda_pose, self.mu0, self.tangent_weight)
+        cfg.c_struct()
+        return cfg
+
+
+_STATE_KEYS = ("pose", "beta", "transl")
+
+
+def _register(what, hands, model_or_layer, points, inits, weights, valids, config):
+    config = config or RegisterConfig()
+    fit_cfg, start_cfg = config.fit_config(), config.fit_config(iters=0)
+    if any(i is None for i in inits):
+        raise ValueError(f"hands_amd: {what} needs init = (pose (B,16,3,3), beta (B,10), transl (B,3)) for every hand: ICP is local")
+    dev = _device_of(points[0], what)
+    packs = [_mano_pack(model_or_layer, h, dev) for h in hands]
+    points = [_opt(p, tuple(p.shape), dev, "points") for p in points]
+    B, P = points[0].shape[:2]
+    # round 0: no iteration, any four rows will do -- it turns init into vertices (and refuses what a fit refuses)
+    face0 = torch.zeros(B, P, dtype=torch.int32, device=dev)
+    bary0 = torch.zeros(B, P, 3, device=dev)
+    bary0[..., 0] = 1.0
+    n = len(hands)
+    state = list(_fit(_FIT_SURF, what, hands, model_or_layer, points, weights, valids, inits, start_cfg,
+                      more=[(face0, bary0, None)] * n))
+    done = [torch.zeros(B, dtype=torch.int32, device=dev) for _ in hands]
+    dist = [torch.full((B, P), float("nan"), device=dev) for _ in hands]
+    for r in range(int(config.rounds)):
+        cor = [correspond_on_mesh(points[i], state[i]["verts"], packs[i]["faces_i32"], weights[i], config.max_dist) for i in range(n)]
+        new = _fit(_FIT_SURF, what, hands, model_or_layer, points, [c["weights"] for c in cor], valids,
+                   [tuple(s[k] for k in _STATE_KEYS) for s in state], fit_cfg,
+                   more=[(c["face_idx"], c["bary"], c["normal"]) for c in cor])
+        for i in range(n):
+            ok = torch.isfinite(new[i]["rmse"])        # a hand whose round is not fitted keeps its state
+            state[i] = xdict({k: torch.where(ok.view((-1,) + (1,) * (v.dim() - 1)), new[i][k], v) for k, v in state[i].items()})
+            done[i] = torch.where(ok, torch.full_like(done[i], r + 1), done[i])
+            dist[i] = cor[i]["dist"]
+    for i in range(n):                                 # round 0's rmse is about its stand-in rows: it says nothing
+        state[i].overwrite("rmse", torch.where(done[i] > 0, state[i]["rmse"], torch.full_like(state[i]["rmse"], float("nan"))))
+        state[i]["dist"], state[i]["rounds_done"] = dist[i], done[i]
+    return tuple(state)
+
+
+def register_mano(points, model_or_layer, side="r", init=None, weights=None, valid=None, config=None) -> xdict:
+    """Register ONE hand of a batch to a point cloud WITHOUT correspondences (data-to-model ICP): ``points`` (B,P,3) in metres
+    on the device, P up to 16384.  ``init`` = (pose (B,16,3,3), beta (B,10), transl (B,3)) is REQUIRED (ValueError without it):
+    ICP is local -- every round pairs a point with the closest point of the CURRENT surface --, so the global rotation and a
+    rough pose have to come from somewhere else: a model's prediction (``register_predictions``) or :func:`fit_mano` /
+    :func:`fit_mano_2d` on keypoints.  ``weights`` (B,P) >= 0 (a point of weight 0 is never read), ``valid`` (B), ``config`` a
+    :class:`RegisterConfig` (untuned defaults).
+
+    Round 0 is a launch without iterations that turns ``init`` into vertices; each of the ``rounds`` is one
+    :func:`correspond_on_mesh` launch and one :func:`fit_mano_surface` launch from the previous state with that round's
+    coefficients, normals and (``max_dist``) trimmed weights.  Nothing synchronises with the host.  A hand whose round comes back
+    not fitted (``max_dist`` left fewer than four points, say) keeps its previous state.
+
+    Returns what :func:`fit_mano_surface` returns for the last fitted round, plus ``dist`` (B,P) of the last correspondence --
+    measured BEFORE the last fit -- and ``rounds_done`` (B) int32, the number of the last round that was fitted (0: none; the
+    outputs are then those of round 0 -- ``init`` and its vertices, or the unfitted outputs for a hand no fit accepts -- and
+    ``rmse`` is NaN).  The loop lowers
+    the cloud's distance to the surface; it does not recover what the cloud does not observe."""
+    return _register("register_mano", (side,), model_or_layer, [points], [init], [weights], [valid], config)[0]
+
+
+def register_mano_hands(points_r, points_l, model, init_r=None, init_l=None, weights_r=None, weights_l=None, valid_r=None,
+                        valid_l=None, config=None):
+    """Both hands of a batch, one fit launch per round for the two (and one correspondence launch per hand): -> (right, left),
+    each what :func:`register_mano` returns.  The two clouds have the same number of points (pad with weight 0)."""
+    return _register("register_mano_hands", "rl", model, [points_r, points_l], [init_r, init_l], [weights_r, weights_l],
+                     [valid_r, valid_l], config)
+
+
+def register_predictions(pred, cloud_r, cloud_l, model, meta_info, weights_r=None, weights_l=None, valid_r=None, valid_l=None,
+                         config=None) -> xdict:
+    """The point-cloud counterpart of :func:`refine_predictions`: move a model's prediction onto ``cloud_{r,l}`` (B,P,3), camera
+    space, metres (a depth camera's back-projected pixels of each hand, say).  The registration starts from the prediction as
+    ``refine_predictions`` does, runs :func:`register_mano_hands` with ``config`` (a :class:`RegisterConfig`), and recomputes the
+    nine MANO-head keys per hand exactly as ``refine_predictions`` does; ``refined.{r,l}`` (B) bool are the rows that moved.  A
+    row that is not registered keeps the prediction's tensors bit for bit."""
+    dev = _device_of(pred["mano.pose.r"], "register_predictions")
+    (config or RegisterConfig()).fit_config()
+    P = model.packed(dev)
+    K = meta_info["intrinsics"].to(device=dev, dtype=torch.float32).contiguous()
+    inits = _prediction_state(pred, P, dev)
+    fits = register_mano_hands(cloud_r, cloud_l, model, inits[0], inits[1], weights_r, weights_l, valid_r, valid_l, config)
+    return _with_refits(pred, fits, model, P, K, dev)

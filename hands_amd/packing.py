@@ -175,6 +175,7 @@ def pack_mano(asset: ManoAsset, device):
         "lbs_weights": t(asset.lbs_weights.astype(np.float32)),
         "tip_ids": t(np.asarray(TIP_IDS, np.int32)), "blend": blend,
         "faces": torch.from_numpy(asset.faces.copy()),
+        "faces_i32": t(asset.faces.astype(np.int32)),      # on the device, for hands_mano_fit_surf_f32 and the registration
         # the tip pack of hands_mano_fit_f32: the rows of the five tip vertices, posedirs as (135, 15) [feature][3 tip + coordinate]
         "tip_v_template": t(vt[tips]), "tip_shapedirs": t(sd[tips]), "tip_lbs_weights": t(_f32(asset.lbs_weights)[tips]),
         "tip_posedirs": t(pd.reshape(135, 778, 3)[:, tips].reshape(135, 15)),

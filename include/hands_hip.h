@@ -943,6 +943,71 @@ int hands_mano_fit_verts_f32(const hands_mano_fit_verts_side* sides, int n_sides
                              hands_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * MANO fitting to surface correspondences (csrc/fit_surf.hip, on csrc/fit_device.h and csrc/fit_mesh_device.h): the 61 unknowns,
+ * the iteration and the priors of hands_mano_fit_verts_f32 with P data rows per hand that are points ON the model's faces.
+ * DESIGN.md section 7 "MANO fitting to surface correspondences and ICP registration" is the specification,
+ * tests/fit_surf_ref.py its fp64 restatement.  Launch and guarantees as hands_mano_fit_verts_f32; the rows stream in tiles of 16
+ * from global memory, so P (1 .. HANDS_FIT_SURF_MAX_P, the same for every hand of a call) bounds time, not memory.
+ *
+ * Per side: points (B,P,3) the targets y_k in metres; face_idx (B,P) int32 in [0, 1538), an index into consts.faces; bary (B,P,3)
+ * the coefficients b_k, finite, neither clamped nor normalised; weights (B,P) >= 0 or NULL (all 1); normals (B,P,3) or NULL; valid
+ * and init_* as hands_mano_fit_side.  c_k = sum_i b_ki v_{faces[f_k][i]}; the residual is sqrt(w_k) A_k (c_k + t - y_k), A_k = I
+ * without normals, with tangent_weight == 1 (the normals are then not read) or for a zero normal, else
+ * A_k = n n^T + sqrt(tangent_weight) (I - n n^T) with n = normals[k] as given.
+ * rmse = sqrt(sum_k w_k |c_k + t - y_k|^2 / sum_k w_k), Euclidean: without A and without the priors.
+ * A row of weight 0 (or of a weight that is negative or no number) is never read: its point, coefficients and normal may be NaN
+ * and its face -1.  A tile of 16 rows whose weights are all zero is skipped; zero-weight rows appended behind the last weighted
+ * one change no bit of any output.  The initial state without init_* is the rest hand under the weighted rigid alignment of its
+ * surface points onto the targets.  Outputs: those of hands_mano_fit_verts_f32 and verts (B,778,3) = the fitted vertices +
+ * transl.  iters == 0 returns the initial state, its rmse, j3d and verts.
+ * A hand is not fitted when valid == 0, fewer than four rows have weight > 0, a weighted row has a weight of +inf, a non-finite
+ * point, coefficient or (where they are read) normal, or a face outside [0, 1538) -- checked before anything is read through
+ * it --, or a given initial value is not finite: the outputs of an unfitted row of hands_mano_fit_verts_f32, verts NaN.
+ * consts: those of hands_mano_fit_verts_f32 and faces (1538,3) int32, vertex indices in [0, 778).
+ * HANDS_EINVAL (nothing launched): the cases of hands_mano_fit_verts_f32 with points / face_idx / bary / verts / faces among the
+ * required pointers, P outside [1, HANDS_FIT_SURF_MAX_P], tangent_weight outside [0, 1] or no number.
+ * --------------------------------------------------------------------------------------------- */
+#define HANDS_FIT_SURF_MAX_P 16384
+typedef struct hands_mano_fit_surf_consts {
+  hands_mano_fit_verts_consts mano;
+  const int32_t* faces;
+} hands_mano_fit_surf_consts;
+
+typedef struct hands_mano_fit_surf_side {
+  hands_mano_fit_surf_consts consts;
+  const float *points, *weights, *valid, *init_pose, *init_beta, *init_transl;
+  float *pose, *beta, *transl, *rmse;
+  int32_t* steps;
+  float *j3d, *verts;
+  const int32_t* face_idx;
+  const float *bary, *normals;
+} hands_mano_fit_surf_side;
+
+typedef struct hands_fit_surf_cfg { /* hands_fit_cfg and the weight of the tangential part of a residual */
+  int iters;
+  double lambda_beta, lambda_pose, mu0, tangent_weight;
+} hands_fit_surf_cfg;
+
+int hands_mano_fit_surf_f32(const hands_mano_fit_surf_side* sides, int n_sides, const hands_fit_surf_cfg* cfg, int B, int P,
+                            hands_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Closest point with what a fit needs (csrc/mesh_correspond.hip, on csrc/mesh_distance_device.h): hands_mesh_closest_f32 -- the
+ * same walk, tie rule, limits, skip rules and NaN / -1 conventions, the same bits in dist, face_idx and closest -- plus, per
+ * query, the coefficients of the closest point on its face, that face's unit normal and a gated weight.  One launch.
+ *   bary[b,p]    the coefficients b with closest ~ sum_i b_i verts[faces[face_idx][i]], from the candidate that gave the minimum
+ *                and in its arithmetic: the plane (1 - v - w, v, w), edge ab (1 - t, t, 0), ac (1 - t, 0, t), bc (0, 1 - t, t);
+ *                NaN where face_idx is -1;
+ *   normal[b,p]  ab x ac / |ab x ac| of that face in fp32, zero for a face whose fp32 normal is zero and where face_idx is -1;
+ *   w_out[b,p]   w_in (1 with w_in NULL) where max_dist <= 0 or dist <= max_dist, else 0 (a NaN dist passes no positive gate).
+ * A query with w_in == 0 (or negative, or no number) is not read: dist NaN, face_idx -1, closest and bary NaN, normal 0, w_out 0.
+ * HANDS_EINVAL (nothing launched): as hands_mesh_closest_f32, and a NULL face_idx, closest, bary, normal or w_out, max_dist no number.
+ * --------------------------------------------------------------------------------------------- */
+int hands_mesh_correspond_f32(const float* points, const float* verts, const int32_t* faces, const float* valid, const float* w_in,
+                              float max_dist, float* dist, int32_t* face_idx, float* closest, float* bary, float* normal,
+                              float* w_out, int B, int P, int V, int F, hands_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The validation loss dict on device, forward only (csrc/loss.hip): compute_loss_light of
  * src/callbacks/loss/loss_arctic_sf.py:20-206 (vector_loss / joints_loss / grasp_loss / render_loss of
  * src/utils/loss_modules.py:97-152) with the weighting and the total of src/models/generic/wrapper.py:19-23,100-115.
